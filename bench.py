@@ -48,6 +48,35 @@ S, A, H, L, B = 60, 2, 1024, 2, 1024
 DP_MODES = ("allreduce_1stream", "reduce_scatter_1stream", "reduce_scatter_pipelined_1comm", "reduce_scatter_pipelined_2comm")
 
 
+DUMP_BUDGET_BYTES = 63_000_000     # --dump-outputs: array data of all files (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write what the timed path computed in its last step as <out_dir>/<name>.npy, float32 kept,
+    anything else as float64.  When the whole set exceeds the budget, each array larger than its share is replaced
+    by a fixed, seeded sample of its elements (flat, indices sorted; the seed is keyed by the name), so that two builds
+    run with the same arguments can be compared element for element."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for name, v in arrays.items():
+        x = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        arrs[name] = x.astype(np.float32 if x.dtype == np.float32 else np.float64, copy=False)
+    left, total = DUMP_BUDGET_BYTES, 0
+    order = sorted(arrs, key=lambda k: (arrs[k].nbytes, k))
+    for i, name in enumerate(order):
+        x = arrs[name]
+        share = left // (len(order) - i)
+        if x.nbytes > share:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            x = x.ravel()[np.sort(rng.choice(x.size, share // x.itemsize, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        left -= x.nbytes
+        total += x.nbytes
+    sys.stderr.write(f"[bench] {len(order)} output arrays ({total / 1e6:.1f} MB) written to {out_dir}\n")
+
+
 def por_flops_per_sample(h=None):
     """14 440 448 MAC per sample at H=1024."""
     h = h or H
@@ -134,9 +163,9 @@ def cpu_baseline(budget_s=12.0):
 # Secondary workloads: BASELINE configs 3 (CQL) and 5 (SORL + costmap encoder).  `--workload cql|sorl_enc` prints their
 # own line; the default run folds a short form of each into `secondary`.
 # =====================================================================================================================
-def measure_cql(steps, warmup, with_cpu=True):
+def measure_cql(steps, warmup, with_cpu=True, dump_dir=None):
     """BASELINE config 3: CQL(H) learn() at B=4096, S=60, A=10, Q-net 64-128-64, 100 k-row buffer resident on the
-    device, rows drawn by the step kernel itself."""
+    device, rows drawn by the step kernel itself.  dump_dir: the last timed step's losses and networks (dump_outputs)."""
     import numpy as np
     import torch
     from porl_amd.train.cql_trainer import CQLTrainer
@@ -164,6 +193,12 @@ def measure_cql(steps, warmup, with_cpu=True):
     el = time.perf_counter() - t0
     if not np.isfinite(t._engine.stats[:3].cpu().numpy()).all():
         raise RuntimeError("non-finite CQL loss")
+    if dump_dir:
+        # [loss, td_loss, cql_penalty] of the last timed step, then the networks it left behind
+        arrays = {"losses": t._engine.stats[:3]}
+        for prefix, net in (("q_network.", t.q_network), ("target_network.", t.target_network)):
+            arrays.update({prefix + k: v for k, v in net.state_dict().items()})
+        dump_outputs(dump_dir, arrays)
     # instrumented second pass: HIP events around the step kernel on its launch stream
     psteps = max(steps, 50)
     E.prof_enable(True)
@@ -231,10 +266,12 @@ def measure_cql(steps, warmup, with_cpu=True):
     return out
 
 
-def measure_sorl_enc(steps, warmup, batch=512, angle_bins=360, dist_bins=256, enc_dtype="fp32", with_cpu=True):
+def measure_sorl_enc(steps, warmup, batch=512, angle_bins=360, dist_bins=256, enc_dtype="fp32", with_cpu=True,
+                     dump_dir=None):
     """BASELINE config 5: SORL.update with the FasterNet costmap encoder as backbone, S = angle_bins + 2 (beams + goal),
     feature_dim=256, H=512.  One step = encode s, encode s' (train-mode BatchNorm, DropPath), value + policy update.
-    fp32 on the reference's 360x256 image is the parity configuration; 84x84 / bf16 are BASELINE's wording."""
+    fp32 on the reference's 360x256 image is the parity configuration; 84x84 / bf16 are BASELINE's wording.
+    dump_dir: the last timed step's losses and the agent's state (dump_outputs)."""
     import numpy as np
     import torch
     from types import SimpleNamespace
@@ -283,6 +320,9 @@ def measure_sorl_enc(steps, warmup, batch=512, angle_bins=360, dist_bins=256, en
     losses = agent._engine.stats[:2].cpu().numpy()
     if not np.isfinite(losses).all():
         raise RuntimeError("non-finite loss in the SORL + encoder run")
+    if dump_dir:
+        # [v_loss, g_loss, min_nll] of the last timed step, then parameters and BatchNorm statistics (encoder included)
+        dump_outputs(dump_dir, {"losses": agent._engine.stats[:3], **agent.state_dict()})
     psteps = min(steps, 10)
     E.prof_enable(True)
     for i in range(psteps):
@@ -488,13 +528,18 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` object (configs 3 / 5, H=256, sync mode)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="issue every update back to back on one stream (profiling: kernels never overlap)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (losses, parameters) as DIR/<name>.npy; "
+                         "the inputs are seeded, so two builds run with the same arguments compare output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.workload == "cql":
-        print(json.dumps(measure_cql(a.steps, a.warmup, not a.no_cpu_baseline)), flush=True)
+        print(json.dumps(measure_cql(a.steps, a.warmup, not a.no_cpu_baseline, a.dump_outputs)), flush=True)
         return
     if a.workload == "sorl_enc":
         print(json.dumps(measure_sorl_enc(a.steps, a.warmup, a.batch or 512, a.angle_bins, a.dist_bins, a.enc_dtype,
-                                          not a.no_cpu_baseline)), flush=True)
+                                          not a.no_cpu_baseline, a.dump_outputs)), flush=True)
         return
     global H, B
     if a.hidden:
@@ -502,6 +547,8 @@ def main():
     if a.batch:
         B = a.batch
     force_dp = os.environ.get("PORL_BENCH_FORCE_DP") == "1"        # one rank, RCCL collectives really issued (tests)
+    if a.dump_outputs and (a.gpus > 1 or force_dp):
+        ap.error("--dump-outputs needs a single-process run (--gpus 1): the data-parallel run times several modes")
     if (a.gpus > 1 or force_dp) and os.environ.get("PORL_BENCH_CHILD") != "1":
         # this process never touches a GPU: it starts the rank process(es) and follows them
         return supervise(a.gpus, launched_by_torchrun="WORLD_SIZE" in os.environ and a.gpus > 1)
@@ -718,6 +765,10 @@ def por_rank(a, force_dp):
     res = timed_run(mode, a.steps, a.warmup, keep=True)
     out = line_for(res, a.steps, a.warmup)
     agent, one_step = res["agent"], res["one_step"]
+    if a.dump_outputs:
+        # before anything below updates the agent again: [v_loss, g_loss, min_nll] of the last timed update and the
+        # networks it left (value twins, their target, goal policy)
+        dump_outputs(a.dump_outputs, {"losses": res["lh"][-1], **agent.state_dict()})
 
     # Not `value`: the same loop again for 1 000 updates, five times, median.  The first ~20 updates after a device sync
     # run ~4 % slower than the steady state (scripts/bench_ramp.py: 315 against 303 us each) and a K = 20 run also pays the
