@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define PORL_ABI_VERSION 5
+#define PORL_ABI_VERSION 6
 #define PORL_MAX_HIDDEN 8
 
 #define PORL_OK 0
@@ -453,9 +453,11 @@ int porl_per_update(double* tree, int64_t capacity, const int64_t* tree_idx, con
 int porl_per_sample(const double* tree, int64_t capacity, const double* u, int32_t batch, int64_t n_entries,
                     double beta, int64_t* out_idx, double* out_prio, float* out_w, void* stream);
 
-/* Experiment knobs (scheduling only, never the mathematics).  "gemm_lds_pad": extra dynamic LDS bytes per GEMM
- * block, limiting how many blocks share a CU.  "qnet_fused": 0 forces the multi-launch CQL path. */
+/* Experiment knobs (scheduling only, never the mathematics).  "gemm_lds_pad": extra dynamic LDS bytes per GEMM block,
+ * limiting how many blocks share a CU.  "qnet_fused": 0 forces the multi-launch CQL path.  porl_tune_set sets the process
+ * defaults, copied by porl_iql / qnet / enc handles when created; porl_iql_tune_set sets one live IQL engine's copy. */
 int porl_tune_set(const char* key, int value);
+int porl_iql_tune_set(porl_iql* h, const char* key, int value);
 /* Diagnostics taking a device pointer.  "qnet_stamps": >= 32 uint64 receiving block 0's shader-clock stamps at
  * the phase boundaries of the one-launch CQL kernel (NULL switches it off). */
 int porl_tune_set_ptr(const char* key, void* ptr);

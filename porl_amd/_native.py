@@ -11,14 +11,14 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libporl_hip.so")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # every symbol include/porl_hip.h declares (tests check the .so exports exactly these)
 SYMBOLS = [
     "porl_abi_version", "porl_last_error",
     "porl_iql_create", "porl_iql_destroy", "porl_iql_group_floats", "porl_iql_group_tensors",
     "porl_iql_tensor_info", "porl_iql_workspace_floats", "porl_iql_bind", "porl_iql_load_batch",
-    "porl_iql_load_batch_sampled", "porl_iql_set_stats", "porl_iql_set_mode",
+    "porl_iql_load_batch_sampled", "porl_iql_set_stats", "porl_iql_set_mode", "porl_iql_tune_set",
     "porl_iql_value_backward", "porl_iql_value_apply", "porl_iql_policy_forward", "porl_iql_policy_backward",
     "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_prefetch", "porl_iql_forward_value", "porl_iql_forward_policy",
     "porl_gemm_f32", "porl_adam_ema", "porl_ema", "porl_softmax_mask", "porl_gather_rows", "porl_sample_indices", "porl_epoch_indices", "porl_per_update", "porl_per_sample",
@@ -126,6 +126,7 @@ def _declare(lib):
     lib.porl_per_update.argtypes = [vp, i64, vp, vp, i32, f64, f64, vp, vp]
     lib.porl_per_sample.argtypes = [vp, i64, vp, i32, i64, f64, vp, vp, vp, vp]
     lib.porl_tune_set.argtypes = [C.c_char_p, C.c_int]
+    lib.porl_iql_tune_set.argtypes = [vp, C.c_char_p, C.c_int]
     lib.porl_tune_set_ptr.argtypes = [C.c_char_p, vp]
     lib.porl_signal_create.argtypes = [C.POINTER(vp)]
     lib.porl_signal_destroy.argtypes = [vp]

@@ -51,6 +51,7 @@ struct porl_enc {
   bool bf16_fused = false;          // cfg.bf16_operands == 2 and the shape is one encoder_bf16.hpp is instantiated for
   int64_t ws_wmerge_bf16 = 0;
   int device = -1;
+  Tune tune = g_tune;               // kernel selection: the process defaults at creation
 };
 
 namespace {
@@ -91,7 +92,7 @@ struct EncEpi {
   bool bf16 = false;               // operands rounded to bf16, fp32 accumulate (gemm_bf16.hpp)
 };
 
-int enc_gemm_rows(hipStream_t s, const float* A, int lda, long rows, const float* Wt, int N, int K, float* C, int ldc,
+int enc_gemm_rows(const porl_enc* h, hipStream_t s, const float* A, int lda, long rows, const float* Wt, int N, int K, float* C, int ldc,
                   const float* bias, int act, const EncEpi& epi = EncEpi()) {
   const long reach = ((1L << 31) - (1L << 20)) / (4L * std::max(lda, ldc));
   const long chunk = std::max<long>(128, reach & ~127L);
@@ -122,13 +123,13 @@ int enc_gemm_rows(hipStream_t s, const float* A, int lda, long rows, const float
     // blocks per CU instead of four) 42.1 with, 44.8 without the 128x96 exception — a block spends ~5 us fetching its
     // first operands and ~2.5 us storing C around 1.5-3 us of matrix work, and only co-resident blocks fill that.
     // porl_tune_set("enc_gemm_sb", 0) / ("enc_tile_n96", 1) bring the other forms back (A/B; results are bit-identical).
-    const bool n96 = N == 96 && g_enc_tile_n96;
+    const bool n96 = N == 96 && h->tune.enc_tile_n96;
     const int tile = (rows >= 4096 && n96 && !epi.bf16) ? TILE_128x96
                      : (rows >= 4096 || epi.a_scale || epi.bf16)
-                         ? ((K >= 384 && !(epi.resid && !epi.bf16)) ? TILE_128x64 : TILE_64x64) : pick_tile(g);
-    g.single_buffer = (rows >= 4096 && tile == TILE_64x64 && g_enc_gemm_sb && K <= 512) ? 1 : 0;
+                         ? ((K >= 384 && !(epi.resid && !epi.bf16)) ? TILE_128x64 : TILE_64x64) : pick_tile(g, h->tune);
+    g.single_buffer = (rows >= 4096 && tile == TILE_64x64 && h->tune.enc_gemm_sb && K <= 512) ? 1 : 0;
     if (epi.bf16) PORL_TRY(launch_group_bf16(g, tile, s));
-    else PORL_TRY(launch_group(g, tile, s));
+    else PORL_TRY(launch_group(g, tile, h->tune, s));
   }
   return 0;
 }
@@ -215,7 +216,7 @@ int enc_pconv_mfma_launch(const float* x, const float* w, float* y, int batch, i
 int enc_pconv(porl_enc* h, const EncBlock& b, const float* x, float* y, float* col, long rows, int Hh, int Ww,
               hipStream_t s) {
   const int batch = (int)(rows / ((long)Hh * Ww));
-  if (g_enc_pconv_mfma && b.dim % 4 == 0 && (b.cp == 24 || b.cp == 48)) {
+  if (h->tune.enc_pconv_mfma && b.dim % 4 == 0 && (b.cp == 24 || b.cp == 48)) {
     const int rc = b.cp == 24 ? enc_pconv_mfma_launch<24>(x, h->W + b.wp_mfma, y, batch, Hh, Ww, b.dim, s)
                               : enc_pconv_mfma_launch<48>(x, h->W + b.wp_mfma, y, batch, Hh, Ww, b.dim, s);
     if (rc >= 0) return rc;
@@ -230,7 +231,7 @@ int enc_pconv(porl_enc* h, const EncBlock& b, const float* x, float* y, float* c
   }
   EncEpi ep;
   ep.bf16 = h->cfg.bf16_operands != 0;
-  return enc_gemm_rows(s, col, 9 * b.cp, rows, h->W + b.wp_packed, b.cp, 9 * b.cp, y, b.dim, nullptr, ACT_NONE, ep);
+  return enc_gemm_rows(h, s, col, 9 * b.cp, rows, h->W + b.wp_packed, b.cp, 9 * b.cp, y, b.dim, nullptr, ACT_NONE, ep);
 }
 
 // one MLPBlock on x (rows, dim) in place; H x W is the position grid of its stage
@@ -246,14 +247,14 @@ int enc_block(porl_enc* h, const EncBlock& b, float* x, long rows, int Hh, int W
   EncEpi e1, e2;
   e1.bf16 = e2.bf16 = h->cfg.bf16_operands != 0;
   if (training) e1.cstat = W + h->ws_cstat;
-  PORL_TRY(enc_gemm_rows(s, y, b.dim, rows, h->params + b.w1, b.hidden, b.dim, hid, b.hidden, nullptr, ACT_NONE, e1));
+  PORL_TRY(enc_gemm_rows(h, s, y, b.dim, rows, h->params + b.w1, b.hidden, b.dim, hid, b.hidden, nullptr, ACT_NONE, e1));
   // BatchNorm + ReLU of the hidden activation: folded into W2's operand staging when the shape allows (the hidden
   // tensor is then read once instead of read + written + read), a separate sweep otherwise
-  const bool fold = (b.hidden % GEMM_BK == 0 || e2.bf16) && b.hidden <= 1024 && !g_enc_bn_sweep;
+  const bool fold = (b.hidden % GEMM_BK == 0 || e2.bf16) && b.hidden <= 1024 && !h->tune.enc_bn_sweep;
   PORL_TRY(enc_batchnorm(h, b.bn, hid, rows, 1, training, s, e1.cstat, !fold));
   if (fold) { e2.a_scale = W + b.bn.alpha; e2.a_shift = W + b.bn.beta; }
   e2.resid = x; e2.rscale = scale; e2.rs_rows = Hh * Ww;
-  PORL_TRY(enc_gemm_rows(s, hid, b.hidden, rows, h->params + b.w2, b.dim, b.hidden, x, b.dim, nullptr, ACT_NONE, e2));
+  PORL_TRY(enc_gemm_rows(h, s, hid, b.hidden, rows, h->params + b.w2, b.dim, b.hidden, x, b.dim, nullptr, ACT_NONE, e2));
   return 0;
 }
 
@@ -478,7 +479,6 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
     PORL_FAIL(PORL_ERR_INVALID, "need 1 <= batch <= max_batch (%d)", h->cfg.max_batch);
   if (feat_rs < h->cfg.num_classes || feat_rs > (1 << 20)) PORL_FAIL(PORL_ERR_INVALID, "bad feature row stride");
   DevGuard _dg(h->device);
-  g_short_blocks = false;
   hipStream_t s = (hipStream_t)stream;
   const porl_enc_cfg& c = h->cfg;
   float* W = h->W;
@@ -518,10 +518,10 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
 
   float* x1 = W + h->ws_x1;
   float* x2 = W + h->ws_x2;
-  const bool sparse_patch = E <= PE_MAX_E && !g_enc_dense_patch &&
+  const bool sparse_patch = E <= PE_MAX_E && !h->tune.enc_dense_patch &&
                             (size_t)PE_K * E * sizeof(float) + (size_t)h->P1 * 12 <= 150 * 1024;
   // bf16-activation mode: needs the sparse patch embedding (it writes bf16 directly); otherwise the bf16-operand mode
-  const bool fused16 = h->bf16_fused && sparse_patch && !g_enc_bf16_operands_only;
+  const bool fused16 = h->bf16_fused && sparse_patch && !h->tune.enc_bf16_operands_only;
   if (sparse_patch) {
     // PatchEmbed + its BatchNorm straight from the lidar state: only the ~6 % non-empty patches are convolved
     // (statistics first, then every position is written once, already normalised); no costmap image at all
@@ -557,7 +557,7 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
       ProfScope ps("patch_bn_kernel", s, 0.0, 4.0 * rows1 * E);
       // patch rows per block: as many as keep >= 4 blocks per CU in the grid, at most 16 (the weight is parked once per
       // block; measured at B = 512, bf16: 84x84 828 -> 888 updates/s, 360x256 123.1 -> 127.8, gpurun_out/r03/prow)
-      int rpb = g_enc_patch_rows > 0 ? g_enc_patch_rows : (int)std::max<long>(1, std::min<long>(16, (long)h->Hp * batch / (4L * NUM_CU)));
+      int rpb = h->tune.enc_patch_rows > 0 ? h->tune.enc_patch_rows : (int)std::max<long>(1, std::min<long>(16, (long)h->Hp * batch / (4L * NUM_CU)));
       rpb = std::min(rpb, h->Hp);
       const dim3 grid(cdiv(h->Hp, rpb), batch);
       if (fused16)
@@ -618,9 +618,9 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
       hipLaunchKernelGGL(gap_bf16_kernel, dim3(batch), dim3(256), 0, s, x2b, W + h->ws_pool, h->P2, E2);
       PORL_HIP(hipGetLastError());
     }
-    PORL_TRY(enc_gemm_rows(s, W + h->ws_pool, E2, batch, h->params + h->w_pre, c.feature_dim, E2, W + h->ws_feat,
+    PORL_TRY(enc_gemm_rows(h, s, W + h->ws_pool, E2, batch, h->params + h->w_pre, c.feature_dim, E2, W + h->ws_feat,
                            c.feature_dim, nullptr, ACT_RELU));
-    PORL_TRY(enc_gemm_rows(s, W + h->ws_feat, c.feature_dim, batch, h->params + h->w_head, c.num_classes, c.feature_dim,
+    PORL_TRY(enc_gemm_rows(h, s, W + h->ws_feat, c.feature_dim, batch, h->params + h->w_head, c.num_classes, c.feature_dim,
                            features, (int)feat_rs, h->params + h->b_head, ACT_NONE));
     return PORL_OK;
   }
@@ -633,7 +633,7 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
   EncEpi em;
   em.bf16 = c.bf16_operands != 0;
   if (training) em.cstat = W + h->ws_cstat;
-  if ((2 * E) % GEMM_BK == 0 && !g_enc_s2d && h->Hp % 2 == 0 && h->Wp % 2 == 0 && !em.bf16) {
+  if ((2 * E) % GEMM_BK == 0 && !h->tune.enc_s2d && h->Hp % 2 == 0 && h->Wp % 2 == 0 && !em.bf16) {
     const int W2 = h->W2;
     const long reach = ((1L << 31) - (1L << 22)) / (4L * 4 * E);          // rows per problem: A spans ~2x (M x 2E)
     const long chunk = std::max<long>(W2, (reach / (32L * W2)) * (32L * W2));   // multiple of 32 rows and of W2
@@ -650,8 +650,8 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
         g.p[g.nprob++] = p;
         done += m;
       }
-      g.single_buffer = (g_enc_gemm_sb & 2) ? 1 : 0;
-      PORL_TRY(launch_group(g, (g_enc_gemm_sb & 2) ? TILE_64x64 : TILE_128x64, s));
+      g.single_buffer = (h->tune.enc_gemm_sb & 2) ? 1 : 0;
+      PORL_TRY(launch_group(g, (h->tune.enc_gemm_sb & 2) ? TILE_64x64 : TILE_128x64, h->tune, s));
     }
   } else {
     {
@@ -661,7 +661,7 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
                          h->Wp, E);
       PORL_HIP(hipGetLastError());
     }
-    PORL_TRY(enc_gemm_rows(s, W + h->ws_col, 4 * E, rows2, W + h->ws_wmerge, E2, 4 * E, x2, E2, nullptr, ACT_NONE, em));
+    PORL_TRY(enc_gemm_rows(h, s, W + h->ws_col, 4 * E, rows2, W + h->ws_wmerge, E2, 4 * E, x2, E2, nullptr, ACT_NONE, em));
   }
   PORL_TRY(enc_batchnorm(h, h->bn_merge, x2, rows2, 0, training, s, em.cstat));
   for (int i = c.depth0; i < c.depth0 + c.depth1; ++i)
@@ -672,9 +672,9 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
     hipLaunchKernelGGL(gap_kernel, dim3(cdiv(E2, 64), batch), dim3(256), 0, s, x2, W + h->ws_pool, h->P2, E2);
     PORL_HIP(hipGetLastError());
   }
-  PORL_TRY(enc_gemm_rows(s, W + h->ws_pool, E2, batch, h->params + h->w_pre, c.feature_dim, E2, W + h->ws_feat,
+  PORL_TRY(enc_gemm_rows(h, s, W + h->ws_pool, E2, batch, h->params + h->w_pre, c.feature_dim, E2, W + h->ws_feat,
                          c.feature_dim, nullptr, ACT_RELU));
-  PORL_TRY(enc_gemm_rows(s, W + h->ws_feat, c.feature_dim, batch, h->params + h->w_head, c.num_classes, c.feature_dim,
+  PORL_TRY(enc_gemm_rows(h, s, W + h->ws_feat, c.feature_dim, batch, h->params + h->w_head, c.num_classes, c.feature_dim,
                          features, (int)feat_rs, h->params + h->b_head, ACT_NONE));
   return PORL_OK;
 }

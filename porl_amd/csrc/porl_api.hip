@@ -108,62 +108,102 @@ struct ProfScope {
 const float* g_dbg_a_scale = nullptr; const float* g_dbg_a_shift = nullptr; const float* g_dbg_resid = nullptr;
 float* g_dbg_cstat = nullptr;
 unsigned long long* g_qnet_stamps = nullptr;   // porl_tune_set_ptr("qnet_stamps", device buffer of >= 32 u64)
-int g_enc_tile_n96 = 0;
-int g_enc_gemm_sb = 1;        // porl_tune_set("enc_gemm_sb", 0): the encoder's 64x64 row products on the double-buffered schedule (A/B)
-int g_enc_patch_rows = 0;     // porl_tune_set("enc_patch_rows", n): patch rows per block of patch_bn_kernel (0 = by grid size; A/B)
-int g_enc_s2d = 0;           // porl_tune_set("enc_s2d", 1): materialise the 2x2 patches before the merge GEMM (cross-check)
-// What pick_tile returns where its occupancy rule selects tile i (porl_tune_set("tile_map<i>", t) / "tile_map_short<i>").
-// Measured on the POR step (gpurun_out/r02, bench.py PORL_TILE_MAP): with two co-resident 64x128 blocks per CU the
-// 4 x 1024^3 launches take 71 instead of 75 us (each block's prologue / C store under the other's MFMA loop), and the
-// 3-net forward / policy backward take 55 / 41 us on 64x64 tiles (768 / 512 blocks = exactly 3 / 2 per CU) instead of
-// 69 / 45 on 128x64 (384 blocks: 1.5 per CU).  SHORT-BLOCK mode (PORL_IQL_MODE_SHORT_BLOCKS, the pipelined update):
-// 64x64 everywhere — alone those launches are slower (77 / 84 us), but a second stream's kernels only get CUs when
-// blocks retire, and 20 us blocks retire often: 2 990 -> 3 110 updates/s.
-int g_tile_map[4] = {TILE_64x128, TILE_64x64, TILE_64x128, TILE_64x64};
-int g_tile_map_short[4] = {TILE_64x64, TILE_64x64, TILE_64x128, TILE_64x64};
-thread_local bool g_short_blocks = false;       // set by the IQL entry points from the handle's mode
-int g_vbwd_tile_short = -1;   // porl_tune_set("vbwd_tile_short", t): tile of the value nets' hidden-layer backward in short-block mode (A/B)
-int g_l0_kernel = 1;        // porl_tune_set("l0_kernel", 0): input layers (K <= 64) through the grouped GEMM instead of l0_fwd_kernel (A/B, bit-identical)
-int g_l0_tile = -1;          // porl_tune_set("l0_tile", t): tile override for the K <= 128 forward layers of the IQL step (A/B)
-// porl_tune_set("skinny", mask): which of the <= 64-wide products of the IQL step run on skinny.hpp instead of the grouped
-// GEMM — bit 0: input-layer weight gradients dW0, bit 1: policy mean, bit 2: policy output-layer backward; 0 = round 2's
-// path (A/B; same sums, other order inside a 64-chunk), 1 is read as "all" (7)
-int g_skinny = 7;
-// The same mask for the PIPELINED update (PORL_IQL_MODE_SHORT_BLOCKS), porl_tune_set("skinny_pipelined", mask).  Default 0:
-// there the policy phase is not the critical stream, and shortening its launches moved the two queues against each other
-// — same-box A/B (gpurun_out/r03/ab3.log, sustained updates/s, two runs each): mask 0: 3 306 / 3 309; 7: 3 206 / 3 204; 4:
-// 3 233 / 3 238; 6: 3 221 / 3 218 — while the one-stream update gains 10-12 us (380 -> 369 us event-timed).
-// Round 3, later: that holds for H = 1024, where the big products dominate.  At H = 256 (B = 1024) the update is a chain
-// of short launches and the skinny kernels are worth +10 % pipelined as well (8 600 -> 9 530 updates/s), at H = 512
-// +0.5 ... +5 % (6 570-6 860 -> 6 890-6 950), at H = 768 +2 % (4 490 -> 4 570), two runs each: -1 = by width — on up to
-// `g_skinny_pipelined_max_h`, off above.
-int g_skinny_pipelined = -1;
-int g_skinny_pipelined_max_h = 768;
-thread_local int g_cur_hidden = 0;              // hidden width of the engine whose entry point is running (check_ready)
-inline int skinny_mask() {
-  if (!g_short_blocks) return g_skinny;
-  if (g_skinny_pipelined >= 0) return g_skinny_pipelined;
-  return g_cur_hidden <= g_skinny_pipelined_max_h ? g_skinny : 0;
-}
-int g_dw0_slabs = 16;        // porl_tune_set("dw0_slabs", n <= SK_MAX): slabs of the skinny dW0 kernel (A/B: fewer slabs = fewer partial bytes, fewer blocks)
-int g_iql_fold = 1;          // porl_tune_set("iql_fold", 0): porl_iql_step keeps the slab combines as launches of their own (A/B)
-int g_enc_bf16_operands_only = 0;   // porl_tune_set("enc_bf16_operands_only", 1): compute_dtype="bf16" runs round 2's bf16-OPERAND mode (fp32 tensors in memory) instead of encoder_bf16.hpp (A/B)
-int g_enc_pconv_mfma = 0;    // porl_tune_set("enc_pconv_mfma", 1): the fp32 partial 3x3 conv as an implicit GEMM on the matrix pipe (round 3) instead of the direct vector-ALU kernel.  Measured SLOWER (5.8 vs 3.7 ms per update at 360x256 B=512): the step moves ~2.5 GB per stage-1 call (input tile, result, the copy of the untouched channels) and is bound by that, not by the 184 GFLOP; the MFMA form parks more LDS per block (77 / 117 KB) and hides less latency.  Kept as a cross-check (tests/test_fasternet_gpu.py)
-int g_enc_bn_sweep = 0;      // porl_tune_set("enc_bn_sweep", 1): BatchNorm + ReLU of the MLP blocks as a separate sweep (cross-check)
-int g_enc_dense_patch = 0;   // porl_tune_set("enc_dense_patch", 1): rasterise + dense patch embedding (cross-check)
-int g_qnet_fused = 1;     // porl_tune_set("qnet_fused", 0) forces the multi-launch CQL path (A/B measurements)
-// 16 rows per block (v_mfma_f32_16x16x4_f32 tiles) while 32-row blocks would leave CUs idle (config 3 at B = 4096: 128 blocks
-// on 256 CUs).  No faster in round 2; with round 3's loss stage on eight lanes per row it is: 22 800 -> 25 300 updates/s,
-// step kernel 41.4 -> 34.6 us event-timed (gpurun_out/r03: same box, two runs each).  porl_tune_set("qnet_rows16", 0) = A/B.
-int g_qnet_rows16 = 1;
-int g_qnet_wgrad_share = 11;   // porl_tune_set("qnet_wgrad_share", s): sixteenths of a 32-tile layer's dW tiles the dW group keeps (16 = all: round 2's split)
-int g_qnet_two_groups = 1;  // porl_tune_set("qnet_two_groups", 0): the one-group (256-thread) step kernel (A/B, bit-identical)
 
 constexpr int NUM_CU = 256;
 constexpr int SK_MAX = 16;
 constexpr int NLL_ROWS_PER_BLOCK = 4;    // one row per wave
 constexpr int LN_ROWS_PER_BLOCK = 8;
 constexpr int HEAD_ROWS_PER_BLOCK = HEAD_ROWS;
+
+// Kernel selection: every integer key of porl_tune_set, with its default.  porl_iql, porl_qnet and porl_enc copy the
+// process defaults (g_tune) when they are created; the entry points without a handle (porl_gemm_f32) read g_tune.
+struct Tune {
+  // What pick_tile returns where its occupancy rule selects tile i ("tile_map<i>" / "tile_map_short<i>").
+  // Measured on the POR step (round 2, bench.py PORL_TILE_MAP): with two co-resident 64x128 blocks per CU the
+  // 4 x 1024^3 launches take 71 instead of 75 us (each block's prologue / C store under the other's MFMA loop), and the
+  // 3-net forward / policy backward take 55 / 41 us on 64x64 tiles (768 / 512 blocks = exactly 3 / 2 per CU) instead of
+  // 69 / 45 on 128x64 (384 blocks: 1.5 per CU).  SHORT-BLOCK mode (PORL_IQL_MODE_SHORT_BLOCKS, the pipelined update):
+  // 64x64 everywhere — alone those launches are slower (77 / 84 us), but a second stream's kernels only get CUs when
+  // blocks retire, and 20 us blocks retire often: 2 990 -> 3 110 updates/s.
+  int tile_map[4] = {TILE_64x128, TILE_64x64, TILE_64x128, TILE_64x64};
+  int tile_map_short[4] = {TILE_64x64, TILE_64x64, TILE_64x128, TILE_64x64};
+  int vbwd_tile_short = -1;   // tile of the value nets' hidden-layer backward in short-block mode (A/B)
+  int l0_kernel = 1;          // 0: input layers (K <= 64) through the grouped GEMM instead of l0_fwd_kernel (A/B, bit-identical)
+  int l0_tile = -1;           // tile override for the K <= 128 forward layers of the IQL step (A/B)
+  // Which of the <= 64-wide products of the IQL step run on skinny.hpp instead of the grouped GEMM — bit 0: input-layer
+  // weight gradients dW0, bit 1: policy mean, bit 2: policy output-layer backward; 0 = round 2's path (A/B; same sums,
+  // other order inside a 64-chunk), 1 is read as "all" (7)
+  int skinny = 7;
+  // The same mask for the PIPELINED update (PORL_IQL_MODE_SHORT_BLOCKS), "skinny_pipelined".  There the policy phase is
+  // not the critical stream, and shortening its launches moved the two queues against each other — same-box A/B
+  // (round 3, sustained updates/s, two runs each): mask 0: 3 306 / 3 309; 7: 3 206 / 3 204; 4:
+  // 3 233 / 3 238; 6: 3 221 / 3 218 — while the one-stream update gains 10-12 us (380 -> 369 us event-timed).
+  // Round 3, later: that holds for H = 1024, where the big products dominate.  At H = 256 (B = 1024) the update is a chain
+  // of short launches and the skinny kernels are worth +10 % pipelined as well (8 600 -> 9 530 updates/s), at H = 512
+  // +0.5 ... +5 % (6 570-6 860 -> 6 890-6 950), at H = 768 +2 % (4 490 -> 4 570), two runs each: -1 = by width — on up to
+  // `skinny_pipelined_max_h`, off above.
+  int skinny_pipelined = -1, skinny_pipelined_max_h = 768;
+  int dw0_slabs = 16;         // slabs of the skinny dW0 kernel (<= SK_MAX; A/B: fewer slabs = fewer partial bytes, fewer blocks)
+  int iql_fold = 1;           // 0: porl_iql_step keeps the slab combines as launches of their own (A/B)
+  int gemm_lds_pad = 0, gemm_lds_pad_min_blocks = 0;   // extra LDS bytes per GEMM block of launches with >= min blocks
+  // Short-block mode (the pipelined update), while gemm_lds_pad is 0: the pad of a GEMM launch of the value / policy phase
+  // whose K is at least iql_pad_min_k, from iql_pad_min_blocks blocks on.  18 KB -> 55 KB per block -> TWO 64x64 blocks
+  // per CU instead of three.  Two effects, both measured (bench.py PORL_IQL_PAD="value,policy,min_blocks",
+  // PORL_GEMM_LDS_PAD; updates/s): (1) wave quantisation — the value nets' 4 x 1024^3 launches have 1 024 blocks: at three
+  // per CU that is one full round of 768 and a ragged one of 256, at two per CU two full rounds (backward launch alone on
+  // the chip: 84.6 -> 73.4 us; the 768-block 3-net forward gets WORSE at two per CU, 55.1 -> 59.1 us); (2) room for the
+  // other stream — a third of every CU's registers and 50 KB of LDS stay free for the policy stream's small kernels
+  // (with a 45 KB pad, i.e. two blocks and NO LDS left over, the update is slower than unpadded: 3 044 vs 3 106).
+  // none 3 106; every GEMM launch 3 256; value phase only 3 248; policy phase only 3 065; only launches of >= 1 000 blocks
+  // 3 270.  Default: the value phase's launches of at least 4 blocks per CU.
+  int iql_pad_value = 18432, iql_pad_policy = 0, iql_pad_min_blocks = 4 * NUM_CU, iql_pad_min_k = 0;
+  int enc_tile_n96 = 0;       // 1: 128x96 blocks for the encoder's N = 96 row product (A/B)
+  int enc_gemm_sb = 1;        // 0: the encoder's 64x64 row products on the double-buffered schedule (A/B)
+  int enc_patch_rows = 0;     // patch rows per block of patch_bn_kernel (0 = by grid size; A/B)
+  int enc_s2d = 0;            // 1: materialise the 2x2 patches before the merge GEMM (cross-check)
+  int enc_bf16_operands_only = 0;   // 1: compute_dtype="bf16" runs round 2's bf16-OPERAND mode (fp32 tensors in memory) instead of encoder_bf16.hpp (A/B)
+  int enc_pconv_mfma = 0;     // 1: the fp32 partial 3x3 conv as an implicit GEMM on the matrix pipe (round 3) instead of the direct vector-ALU kernel.  Measured SLOWER (5.8 vs 3.7 ms per update at 360x256 B=512): the step moves ~2.5 GB per stage-1 call (input tile, result, the copy of the untouched channels) and is bound by that, not by the 184 GFLOP; the MFMA form parks more LDS per block (77 / 117 KB) and hides less latency.  Kept as a cross-check (tests/test_fasternet_gpu.py)
+  int enc_bn_sweep = 0;       // 1: BatchNorm + ReLU of the MLP blocks as a separate sweep (cross-check)
+  int enc_dense_patch = 0;    // 1: rasterise + dense patch embedding (cross-check)
+  int qnet_fused = 1;         // 0 forces the multi-launch CQL path (A/B measurements)
+  // 16 rows per block (v_mfma_f32_16x16x4_f32 tiles) while 32-row blocks would leave CUs idle (config 3 at B = 4096: 128 blocks
+  // on 256 CUs).  No faster in round 2; with round 3's loss stage on eight lanes per row it is: 22 800 -> 25 300 updates/s,
+  // step kernel 41.4 -> 34.6 us event-timed (round 3: same box, two runs each).  0 = A/B.
+  int qnet_rows16 = 1;
+  int qnet_wgrad_share = 11;  // sixteenths of a 32-tile layer's dW tiles the dW group keeps (16 = all: round 2's split)
+  int qnet_two_groups = 1;    // 0: the one-group (256-thread) step kernel (A/B, bit-identical)
+} g_tune;
+
+// How porl_tune_set reads a value: as given, as 0 / 1, at least 0, clamped to [1, 16], or as a skinny mask (1 = all)
+enum TuneClamp { TC_ANY, TC_BOOL, TC_NONNEG, TC_1_16, TC_MASK };
+struct TuneKey { const char* key; int Tune::*field; TuneClamp clamp; };
+#define TK(key, clamp) {#key, &Tune::key, clamp}     // the key is the field's name
+const TuneKey k_tune_keys[] = {
+    TK(gemm_lds_pad, TC_NONNEG), TK(gemm_lds_pad_min_blocks, TC_NONNEG), TK(iql_pad_value, TC_NONNEG), TK(iql_pad_policy, TC_NONNEG),
+    TK(iql_pad_min_blocks, TC_NONNEG), TK(iql_pad_min_k, TC_NONNEG), TK(qnet_fused, TC_BOOL), TK(qnet_two_groups, TC_BOOL),
+    TK(qnet_wgrad_share, TC_1_16), TK(qnet_rows16, TC_BOOL), TK(enc_dense_patch, TC_BOOL), TK(enc_s2d, TC_BOOL), TK(enc_patch_rows, TC_NONNEG),
+    TK(enc_gemm_sb, TC_ANY), TK(enc_tile_n96, TC_BOOL), TK(enc_bn_sweep, TC_BOOL), TK(enc_pconv_mfma, TC_BOOL), TK(enc_bf16_operands_only, TC_BOOL),
+    TK(iql_fold, TC_BOOL), TK(skinny, TC_MASK), TK(skinny_pipelined, TC_MASK), TK(skinny_pipelined_max_h, TC_ANY), TK(dw0_slabs, TC_1_16),
+    TK(l0_tile, TC_ANY), TK(l0_kernel, TC_BOOL), TK(vbwd_tile_short, TC_ANY),
+};
+
+int tune_apply(Tune& t, const char* key, int value) {
+  if (!key) PORL_FAIL(PORL_ERR_INVALID, "null key");
+  for (const TuneKey& k : k_tune_keys) {
+    if (strcmp(key, k.key)) continue;
+    const TuneClamp c = k.clamp;
+    t.*k.field = c == TC_BOOL ? value != 0 : c == TC_NONNEG ? std::max(0, value) : c == TC_1_16 ? std::max(1, std::min(value, 16))
+               : c == TC_MASK && value == 1 ? 7 : value;
+    return PORL_OK;
+  }
+  const bool sh = !strncmp(key, "tile_map_short", 14);
+  const char* i = key + (sh ? 14 : 8);
+  if (!strncmp(key, "tile_map", 8) && *i >= '0' && *i <= '3' && !i[1] && value >= 0 && value < TILE_COUNT) {
+    (sh ? t.tile_map_short : t.tile_map)[*i - '0'] = value;
+    return PORL_OK;
+  }
+  PORL_FAIL(PORL_ERR_INVALID, "unknown tuning key '%s'", key);
+}
 
 inline int64_t ru4(int64_t x) { return (x + 3) & ~int64_t(3); }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -242,12 +282,13 @@ struct porl_iql {
   int pol_nslab = 1;
   int Sp = 0, Dp = 0, Hp = 0, parts_max = 0;
   Workspace ws{};
+  Tune tune = g_tune;               // kernel selection: the process defaults at creation, porl_iql_tune_set
 };
 
 namespace {
 
 // ---- launch helpers -------------------------------------------------------------------------------
-int pick_tile(const GemmGroup& g) {
+int pick_tile(const GemmGroup& g, const Tune& t, bool short_blocks = false) {
   int minM = 1 << 30, minN = 1 << 30, maxK = 0;
   for (int i = 0; i < g.nprob; ++i) {
     minM = std::min(minM, g.p[i].M); minN = std::min(minN, g.p[i].N); maxK = std::max(maxK, g.p[i].K);
@@ -265,9 +306,10 @@ int pick_tile(const GemmGroup& g) {
   else if (minN <= 64) { cand[nc++] = TILE_128x64; cand[nc++] = TILE_64x64; }
   else if (minM <= 64) { cand[nc++] = TILE_64x128; cand[nc++] = TILE_64x64; }
   else { cand[nc++] = TILE_128x128; cand[nc++] = TILE_128x64; cand[nc++] = TILE_64x64; }
+  const int* map = short_blocks ? t.tile_map_short : t.tile_map;
   for (int i = 0; i < nc; ++i)
-    if (blocks(cand[i]) >= NUM_CU) return (g_short_blocks ? g_tile_map_short : g_tile_map)[cand[i]];
-  return (g_short_blocks ? g_tile_map_short : g_tile_map)[cand[nc - 1]];
+    if (blocks(cand[i]) >= NUM_CU) return map[cand[i]];
+  return map[cand[nc - 1]];
 }
 
 // split-K factor for an output too small to fill the chip on its own
@@ -278,30 +320,11 @@ int pick_splitk(int M, int N, int K, int nprob, int bm, int bn) {
   return std::max(1, std::min(sk, SK_MAX));
 }
 
-// Short-block mode (the pipelined update): how much dynamic LDS a GEMM block of the value ('V') / policy ('P') phase
-// claims on top of its 36 KB of staging buffers, and from how many blocks per launch on.  18 KB -> 55 KB per block ->
-// TWO 64x64 blocks per CU instead of three.  Two effects, both measured (bench.py PORL_IQL_PAD="value,policy,min_blocks",
-// PORL_GEMM_LDS_PAD; updates/s): (1) wave quantisation — the value nets' 4 x 1024^3 launches have 1 024 blocks: at three
-// per CU that is one full round of 768 and a ragged one of 256, at two per CU two full rounds (backward launch alone on
-// the chip: 84.6 -> 73.4 us; the 768-block 3-net forward gets WORSE at two per CU, 55.1 -> 59.1 us); (2) room for the
-// other stream — a third of every CU's registers and 50 KB of LDS stay free for the policy stream's small kernels
-// (with a 45 KB pad, i.e. two blocks and NO LDS left over, the update is slower than unpadded: 3 044 vs 3 106).
-// none 3 106; every GEMM launch 3 256; value phase only 3 248; policy phase only 3 065; only launches of >= 1 000 blocks
-// 3 270.  Default: the value phase's launches of at least 4 blocks per CU.
-int g_iql_pad_value = 18432, g_iql_pad_policy = 0, g_iql_pad_min_blocks = 4 * NUM_CU, g_iql_pad_min_k = 0;
-struct PadScope {
-  int saved, saved_min;
-  explicit PadScope(const GemmGroup& g) : saved(gemm_lds_pad()), saved_min(gemm_lds_pad_min_blocks()) {
-    if (g_short_blocks && saved == 0 && g.nprob > 0 && g.p[0].K >= g_iql_pad_min_k) {
-      gemm_lds_pad() = g_phase[0] == 'P' ? g_iql_pad_policy : g_iql_pad_value;
-      gemm_lds_pad_min_blocks() = g_iql_pad_min_blocks;
-    }
-  }
-  ~PadScope() { gemm_lds_pad() = saved; gemm_lds_pad_min_blocks() = saved_min; }
-};
-
-int launch_group(GemmGroup& g, int tile, hipStream_t s) {
-  PadScope _pad(g);
+// iql_pad >= 0: a launch of the short-block IQL update, whose phase pads by iql_pad (Tune::iql_pad_value / _policy)
+int launch_group(GemmGroup& g, int tile, const Tune& t, hipStream_t s, int iql_pad = -1) {
+  const bool iql = iql_pad >= 0 && !t.gemm_lds_pad && g.nprob > 0 && g.p[0].K >= t.iql_pad_min_k;
+  g.lds_pad = iql ? iql_pad : t.gemm_lds_pad;
+  g.lds_pad_min_blocks = iql ? t.iql_pad_min_blocks : t.gemm_lds_pad_min_blocks;
   double flops = 0.0, bytes = 0.0;
   std::string label;
   if (g_prof.on) {
@@ -376,9 +399,21 @@ int check_ready(const porl_iql* h, bool need_batch) {
   if (!h) PORL_FAIL(PORL_ERR_INVALID, "null engine");
   if (!h->bound) PORL_FAIL(PORL_ERR_UNBOUND, "porl_iql_bind() has not been called");
   if (need_batch && h->batch <= 0) PORL_FAIL(PORL_ERR_INVALID, "no minibatch loaded (porl_iql_load_batch)");
-  g_short_blocks = (h->mode & PORL_IQL_MODE_SHORT_BLOCKS) != 0;
-  g_cur_hidden = h->cfg.hidden_dim;
   return 0;
+}
+
+bool short_blocks(const porl_iql* h) { return (h->mode & PORL_IQL_MODE_SHORT_BLOCKS) != 0; }
+int skinny_mask(const porl_iql* h) {
+  const Tune& t = h->tune;
+  if (!short_blocks(h)) return t.skinny;
+  return t.skinny_pipelined >= 0 ? t.skinny_pipelined : h->cfg.hidden_dim <= t.skinny_pipelined_max_h ? t.skinny : 0;
+}
+int iql_tile(const porl_iql* h, const GemmGroup& g) { return pick_tile(g, h->tune, short_blocks(h)); }
+
+// `policy`: a launch of the update's policy phase (outside the two phases of an update the value pad applies)
+int iql_launch(const porl_iql* h, GemmGroup& g, int tile, bool policy, hipStream_t s) {
+  const Tune& t = h->tune;
+  return launch_group(g, tile, t, s, !short_blocks(h) ? -1 : policy ? t.iql_pad_policy : t.iql_pad_value);
 }
 
 // One hidden layer of up to 4 MLPs as one grouped launch (+ one LayerNorm launch for the nets that have it).
@@ -391,11 +426,11 @@ struct FwdNet {
   float* xhat = nullptr; float* rstd = nullptr;              // kept for backward when non-null
 };
 
-int fwd_hidden_layer(porl_iql* h, const FwdNet* nets, int nnets, int B, int K, bool last, int* parts_out,
+int fwd_hidden_layer(porl_iql* h, const FwdNet* nets, int nnets, int B, int K, bool last, int* parts_out, bool policy,
                      hipStream_t s) {
   const int H = h->cfg.hidden_dim;
   // input layer (K = obs_dim <= 64), plain Linear + ReLU with a stored output: its own one-round kernel (l0_fwd.hpp)
-  if (g_l0_kernel && K <= L0_KP && nnets <= L0_MAX_NETS) {
+  if (h->tune.l0_kernel && K <= L0_KP && nnets <= L0_MAX_NETS) {
     L0Args a{};
     a.nnets = nnets; a.B = B; a.H = H; a.K = K; a.ldw = K; a.ldo = h->Hp;
     bool plain = true;
@@ -424,9 +459,9 @@ int fwd_hidden_layer(porl_iql* h, const FwdNet* nets, int nnets, int B, int K, b
     if (!ln && last && nets[n].headw) { p.headw = nets[n].headw; p.headout = nets[n].headout; }
     g.p[n] = p;
   }
-  const int tile = (K <= 128 && g_l0_tile >= 0) ? g_l0_tile : pick_tile(g);
+  const int tile = (K <= 128 && h->tune.l0_tile >= 0) ? h->tune.l0_tile : iql_tile(h, g);
   if (parts_out) *parts_out = any_ln ? 1 : head_parts(H, tile);
-  PORL_TRY(launch_group(g, tile, s));
+  PORL_TRY(iql_launch(h, g, tile, policy, s));
   if (any_ln) {
     LnFwdArgs a{};
     for (int n = 0; n < nnets; ++n) {
@@ -624,7 +659,7 @@ static int value_backward_ln(porl_iql* h, const porl_iql_hyper* hp, hipStream_t 
       if (l > 0)   // unmasked: the ReLU mask of layer l-1 is applied by its own LayerNorm backward
         g.p[g.nprob++] = make_prob(GEMM_NN, dz, Hp, Pv + h->v[i].w[l], Kin, W + ws.dz_v[i][0], Hp, B, Kin, H);
     }
-    const int tile = pick_tile(g);
+    const int tile = iql_tile(h, g);
     if (l == 0) {
       int bm, bn;
       tile_dims(tile, bm, bn);
@@ -640,7 +675,7 @@ static int value_backward_ln(porl_iql* h, const porl_iql_hyper* hp, hipStream_t 
         }
       }
     }
-    PORL_TRY(launch_group(g, tile, s));
+    PORL_TRY(iql_launch(h, g, tile, false, s));
     if (l == 0 && defer) *defer = red;       // only the last combine can wait for the Adam launch: the LayerNorm
     else PORL_TRY(launch_reduce(red, s));    // partial buffers are reused layer by layer
   }
@@ -705,15 +740,15 @@ int porl_iql_set_stats(porl_iql* h, float* stats) {
 // batch chunks in the split-K layout, combine jobs appended to `red`.  Returns false when the shapes do not qualify
 // (the caller then takes the grouped-GEMM path).
 struct Dw0Net { const float* dz; float* gw; float* gb; float* slabW; float* slabC; };
-static bool dw0_skinny(const Dw0Net* nets, int nnets, const float* X, int ldx, int B, int H, int S, int ldz, ReduceArgs& red,
-                       const char* phase, hipStream_t s, int* rc) {
+static bool dw0_skinny(const porl_iql* h, const Dw0Net* nets, int nnets, const float* X, int ldx, int B, int H, int S, int ldz,
+                       ReduceArgs& red, const char* phase, hipStream_t s, int* rc) {
   *rc = 0;
-  if (!(skinny_mask() & 1) || S > SKN_T || nnets > SKN_MAX_NETS || H % 4 || !skn_ok4(X, ldx) || ldz % 4) return false;
+  if (!(skinny_mask(h) & 1) || S > SKN_T || nnets > SKN_MAX_NETS || H % 4 || !skn_ok4(X, ldx) || ldz % 4) return false;
   for (int i = 0; i < nnets; ++i) if (!skn_ok4(nets[i].dz, ldz)) return false;
   WgradSkinnyArgs a{};
   a.nnets = nnets; a.B = B; a.H = H; a.S = S; a.ldz = ldz; a.ldx = ldx; a.ldo = S;
   a.tiles_n = cdiv(H, SKN_T);
-  skn_split(cdiv(B, SKN_T), g_dw0_slabs, a.nslab, a.rtiles);
+  skn_split(cdiv(B, SKN_T), h->tune.dw0_slabs, a.nslab, a.rtiles);
   a.slabW_stride = (long)H * S; a.slabC_stride = H;
   for (int i = 0; i < nnets; ++i) {
     a.net[i] = WgradSkinnyNet{nets[i].dz, X, nets[i].slabW, nets[i].slabC};
@@ -767,7 +802,7 @@ static int value_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream_
       }
     }
     g_phase = l == 0 ? "V2.L0fwd:" : "V3.fwd:";
-    PORL_TRY(fwd_hidden_layer(h, nets, 4, B, K, l == L - 1, &parts, s));
+    PORL_TRY(fwd_hidden_layer(h, nets, 4, B, K, l == L - 1, &parts, false, s));
   }
   g_phase = "V4.head:";
 
@@ -821,7 +856,7 @@ static int value_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream_
         dn[i] = Dw0Net{W + ws.dz_v[i][0], Gv + h->v[i].w[0], Gv + h->v[i].b[0], slabW, slabW + (int64_t)SK_MAX * per};
       }
       int rc = 0;
-      if (dw0_skinny(dn, 2, W + ws.xs_slot[h->slot], h->Sp, B, H, S, Hp, red, "V6.dW0:", s, &rc)) {
+      if (dw0_skinny(h, dn, 2, W + ws.xs_slot[h->slot], h->Sp, B, H, S, Hp, red, "V6.dW0:", s, &rc)) {
         if (rc) return rc;
         break;
       }
@@ -840,8 +875,8 @@ static int value_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream_
         g.p[g.nprob++] = q;
       }
     }
-    int tile = pick_tile(g);
-    if (l > 0 && g_short_blocks && g_vbwd_tile_short >= 0) tile = g_vbwd_tile_short;
+    int tile = iql_tile(h, g);
+    if (l > 0 && short_blocks(h) && h->tune.vbwd_tile_short >= 0) tile = h->tune.vbwd_tile_short;
     if (l == 0) {
       // skinny (H x S) weight gradient: split the batch (K) dimension to fill the chip
       int bm, bn;
@@ -859,7 +894,7 @@ static int value_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream_
       }
     }
     g_phase = l == 0 ? "V6.dW0:" : "V5.bwd:";
-    PORL_TRY(launch_group(g, tile, s));
+    PORL_TRY(iql_launch(h, g, tile, false, s));
   }
   g_phase = "V7.combine:";
   if (defer) *defer = red;
@@ -962,10 +997,10 @@ int porl_iql_policy_apply(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
 
 // ---------------------------------------------------------------------------------------------------
 // policy mean (pre-bias, pre-activation) as split-K slabs: act_p[L-1] (B,H) x W_L^T (H,D)
-static int policy_mean_slabs(porl_iql* h, int B, int* nslab, hipStream_t s) {
+static int policy_mean_slabs(porl_iql* h, int B, int* nslab, bool policy, hipStream_t s) {
   const int H = h->cfg.hidden_dim, D = h->cfg.pol_out_dim, L = h->cfg.n_hidden;
   float* W = h->buf.workspace;
-  if ((skinny_mask() & 2) && D <= SKN_T && H % 4 == 0 && skn_ok4(W + h->ws.act_p[L - 1], h->Hp) &&
+  if ((skinny_mask(h) & 2) && D <= SKN_T && H % 4 == 0 && skn_ok4(W + h->ws.act_p[L - 1], h->Hp) &&
       skn_ok4(h->buf.params_pol + h->pol.w[L], H) && h->Dp % 4 == 0) {
     MeanSkinnyArgs a{};
     a.A = W + h->ws.act_p[L - 1]; a.W = h->buf.params_pol + h->pol.w[L]; a.slab = W + h->ws.slab_mean;
@@ -985,7 +1020,7 @@ static int policy_mean_slabs(porl_iql* h, int B, int* nslab, hipStream_t s) {
   g.nprob = 1;
   g.p[0] = make_prob(GEMM_NT, W + h->ws.act_p[L - 1], h->Hp, h->buf.params_pol + h->pol.w[L], H, W + h->ws.slab_mean,
                      h->Dp, B, D, H);
-  const int tile = pick_tile(g);
+  const int tile = iql_tile(h, g);
   int bm, bn;
   tile_dims(tile, bm, bn);
   const int sk = pick_splitk(B, D, H, 1, bm, bn);
@@ -993,7 +1028,7 @@ static int policy_mean_slabs(porl_iql* h, int B, int* nslab, hipStream_t s) {
   g.p[0].splitk = sk;
   *nslab = sk;
   if (sk == 1) { g.p[0].bias = nullptr; g.p[0].act = ACT_NONE; }
-  return launch_group(g, tile, s);
+  return iql_launch(h, g, tile, policy, s);
 }
 
 // The part of the policy step that does not depend on the value networks: the policy MLP's forward on the loaded
@@ -1013,9 +1048,9 @@ int porl_iql_policy_prefetch(porl_iql* h, void* stream) {
     else { f.in = W + ws.act_p[l - 1]; f.ldin = h->Hp; }
     f.W = Pp + h->pol.w[l]; f.b = Pp + h->pol.b[l];
     f.out = W + ws.act_p[l]; f.headw = nullptr; f.headout = nullptr;
-    PORL_TRY(fwd_hidden_layer(h, &f, 1, B, l == 0 ? S : H, l == L - 1, &parts, s));
+    PORL_TRY(fwd_hidden_layer(h, &f, 1, B, l == 0 ? S : H, l == L - 1, &parts, false, s));
   }
-  PORL_TRY(policy_mean_slabs(h, B, &h->pol_nslab, s));
+  PORL_TRY(policy_mean_slabs(h, B, &h->pol_nslab, false, s));
   h->pol_prefetched = true;
   return PORL_OK;
 }
@@ -1061,11 +1096,11 @@ static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream
     f.W = Pp + h->pol.w[l]; f.b = Pp + h->pol.b[l];
     f.out = W + ws.act_p[l]; f.headw = nullptr; f.headout = nullptr;
     g_phase = l == 0 ? "P1.L0fwd:" : "P2.fwd:";
-    PORL_TRY(fwd_hidden_layer(h, nets, pre ? 2 : 3, B, K, last, &parts, s));
+    PORL_TRY(fwd_hidden_layer(h, nets, pre ? 2 : 3, B, K, last, &parts, true, s));
   }
   int nslab = h->pol_nslab;
   g_phase = "P3.mean:";
-  if (!pre) PORL_TRY(policy_mean_slabs(h, B, &nslab, s));
+  if (!pre) PORL_TRY(policy_mean_slabs(h, B, &nslab, true, s));
   g_phase = "P4.";
 
   // -- advantage weights, NLL, dL/dmean, dL/dlog_std --------------------------------------------------
@@ -1095,7 +1130,7 @@ static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream
   add_reduce(red, Gp + h->logstd_off, W + ws.part_dls, D, D, nblk);            // d/dlog_std (already clamp-masked)
   add_reduce(red, h->buf.stats + 1, W + ws.part_loss, 1, 1, nblk);            // stats[1] = g_loss
   add_reduce(red, h->buf.stats + 2, W + ws.part_min, 1, 1, nblk, /*min*/ 1);  // stats[2] = min NLL
-  if ((skinny_mask() & 4) && D <= SKN_T && H % 4 == 0 && Dp % 4 == 0 && Hp % 4 == 0 && skn_ok4(Pp + h->pol.w[L], H)) {
+  if ((skinny_mask(h) & 4) && D <= SKN_T && H % 4 == 0 && Dp % 4 == 0 && Hp % 4 == 0 && skn_ok4(Pp + h->pol.w[L], H)) {
     // output layer on out_bwd_kernel (skinny.hpp): one pass over the last hidden activation gives dZ_{L-1} and the
     // dW_L / db_L slabs
     OutBwdArgs a{};
@@ -1123,7 +1158,7 @@ static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream
     g.p[0].colsum = Gp + h->pol.b[L];
     g.p[1] = make_prob(GEMM_NN, W + ws.dmu, Dp, Pp + h->pol.w[L], H, W + ws.dz_p[(L - 1) & 1], Hp, B, H, D);
     g.p[1].mask = W + ws.act_p[L - 1]; g.p[1].ldmask = Hp;
-    const int tile = D <= 64 ? TILE_64x128 : pick_tile(g);
+    const int tile = D <= 64 ? TILE_64x128 : iql_tile(h, g);
     int bm, bn;
     tile_dims(tile, bm, bn);
     const int sk = pick_splitk(D, H, B, 1, bm, bn);
@@ -1135,7 +1170,7 @@ static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream
       add_reduce(red, Gp + h->pol.b[L], slabC, D, D, sk);
     }
     g_phase = "P5.outbwd:";
-    PORL_TRY(launch_group(g, tile, s));
+    PORL_TRY(iql_launch(h, g, tile, true, s));
   }
   for (int l = L - 1; l >= 0; --l) {
     const int Kin = l == 0 ? S : H;
@@ -1144,7 +1179,7 @@ static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream
       float* slabW = W + ws.slab_pa;
       Dw0Net dn{W + ws.dz_p[0], Gp + h->pol.w[0], Gp + h->pol.b[0], slabW, slabW + (int64_t)SK_MAX * per};
       int rc = 0;
-      if (dw0_skinny(&dn, 1, W + ws.xs_slot[h->slot], h->Sp, B, H, S, Hp, red, "P7.dW0:", s, &rc)) {
+      if (dw0_skinny(h, &dn, 1, W + ws.xs_slot[h->slot], h->Sp, B, H, S, Hp, red, "P7.dW0:", s, &rc)) {
         if (rc) return rc;
         break;
       }
@@ -1160,7 +1195,7 @@ static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream
       q.mask = W + ws.act_p[l - 1]; q.ldmask = Hp;
       g.p[g.nprob++] = q;
     }
-    const int tile = pick_tile(g);
+    const int tile = iql_tile(h, g);
     if (l == 0) {
       int bm, bn;
       tile_dims(tile, bm, bn);
@@ -1175,7 +1210,7 @@ static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream
       }
     }
     g_phase = l == 0 ? "P7.dW0:" : "P6.bwd:";
-    PORL_TRY(launch_group(g, tile, s));
+    PORL_TRY(iql_launch(h, g, tile, true, s));
   }
   g_phase = "P8.combine:";
   if (defer) *defer = red;
@@ -1207,12 +1242,12 @@ int porl_iql_step(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
   if (!hp) PORL_FAIL(PORL_ERR_INVALID, "null hyper-parameters");
   hipStream_t s = (hipStream_t)stream;
   ReduceArgs fin{};
-  PORL_TRY(value_backward_impl(h, hp, s, g_iql_fold ? &fin : nullptr));
+  PORL_TRY(value_backward_impl(h, hp, s, h->tune.iql_fold ? &fin : nullptr));
   g_phase = "V8.";
   PORL_TRY(adam_launch(h->buf.params_vf, h->buf.grads_vf, h->buf.adam_m_vf, h->buf.adam_v_vf, h->buf.params_tgt, h->n_vf,
                        hp->value_lr, hp->value_step, hp->adam_beta1, hp->adam_beta2, hp->adam_eps, hp->ema_beta, s, &fin));
   fin = ReduceArgs{};
-  PORL_TRY(policy_backward_impl(h, hp, s, g_iql_fold ? &fin : nullptr));
+  PORL_TRY(policy_backward_impl(h, hp, s, h->tune.iql_fold ? &fin : nullptr));
   g_phase = "P9.";
   PORL_TRY(adam_launch(h->buf.params_pol, h->buf.grads_pol, h->buf.adam_m_pol, h->buf.adam_v_pol, nullptr, h->n_pol,
                        hp->policy_lr, hp->policy_step, hp->adam_beta1, hp->adam_beta2, hp->adam_eps, 0.0, s, &fin));
@@ -1293,7 +1328,7 @@ int porl_iql_forward_value(porl_iql* h, int which, const float* x, int64_t x_rs,
       f.headw = P + h->v[i].w[L]; f.headout = W + h->ws.hp_t[i];
       if (LN) { f.ln_g = P + h->v[i].lnw[l]; f.ln_b = P + h->v[i].lnb[l]; }
     }
-    PORL_TRY(fwd_hidden_layer(h, nets, 2, batch, l == 0 ? S : H, l == L - 1, &parts, s));
+    PORL_TRY(fwd_hidden_layer(h, nets, 2, batch, l == 0 ? S : H, l == L - 1, &parts, false, s));
   }
   hipLaunchKernelGGL(head_finish_kernel, dim3(cdiv(batch, 256)), dim3(256), 0, s, W + h->ws.hp_t[0], W + h->ws.hp_t[1],
                      P + h->v[0].b[L], P + h->v[1].b[L], parts, batch, v1_out, v2_out);
@@ -1335,10 +1370,10 @@ int porl_iql_forward_policy(porl_iql* h, const float* x, int64_t x_rs, int32_t b
     if (l == 0) { f.in = W + h->ws.xn; f.ldin = h->Sp; }
     else { f.in = W + h->ws.act_p[l - 1]; f.ldin = h->Hp; }
     f.W = P + h->pol.w[l]; f.b = P + h->pol.b[l]; f.out = W + h->ws.act_p[l];
-    PORL_TRY(fwd_hidden_layer(h, &f, 1, batch, l == 0 ? S : H, false, nullptr, s));
+    PORL_TRY(fwd_hidden_layer(h, &f, 1, batch, l == 0 ? S : H, false, nullptr, false, s));
   }
   int nslab = 1;
-  PORL_TRY(policy_mean_slabs(h, batch, &nslab, s));
+  PORL_TRY(policy_mean_slabs(h, batch, &nslab, false, s));
   const long n = (long)batch * D;
   hipLaunchKernelGGL(mean_finish_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 1024)), dim3(256), 0, s,
                      W + h->ws.slab_mean, nslab, (long)batch * h->Dp, batch, D, h->Dp, P + h->pol.b[L],
@@ -1351,7 +1386,6 @@ int porl_iql_forward_policy(porl_iql* h, const float* x, int64_t x_rs, int32_t b
 int porl_gemm_f32(int mode, int tile, int32_t M, int32_t N, int32_t K, const float* A, int32_t lda, const float* B,
                   int32_t ldb, float* C, int32_t ldc, const float* bias, int act, const float* mask, int32_t ldmask,
                   int splitk, float* slab, void* stream) {
-  g_short_blocks = false;
   if (mode < 0 || mode > 2) PORL_FAIL(PORL_ERR_INVALID, "mode must be 0..2");
   if (M < 1 || N < 1 || K < 0 || !A || !B || !C) PORL_FAIL(PORL_ERR_INVALID, "bad GEMM arguments");
   if (splitk > 1 && !slab) PORL_FAIL(PORL_ERR_INVALID, "splitk > 1 needs a slab buffer");
@@ -1361,11 +1395,11 @@ int porl_gemm_f32(int mode, int tile, int32_t M, int32_t N, int32_t K, const flo
   GemmGroup g{};
   g.nprob = 1;
   g.p[0] = make_prob(mode, A, lda, B, ldb, C, ldc, M, N, K);
-  if (tile < 0) tile = pick_tile(g);
+  if (tile < 0) tile = pick_tile(g, g_tune);
   if (tile >= TILE_COUNT) PORL_FAIL(PORL_ERR_INVALID, "tile must be -1..%d", TILE_COUNT - 1);
   if (splitk > 1) {
     g.p[0].splitk = splitk; g.p[0].C = slab;
-    PORL_TRY(launch_group(g, tile, s));
+    PORL_TRY(launch_group(g, tile, g_tune, s));
     // rows of the slab have stride ldc; combine all M*ldc floats (padding columns carry garbage that the
     // caller's ldc padding tolerates), then apply bias/act/mask per element
     if (mask) PORL_FAIL(PORL_ERR_UNSUPPORTED, "mask with splitk");
@@ -1381,7 +1415,7 @@ int porl_gemm_f32(int mode, int tile, int32_t M, int32_t N, int32_t K, const flo
   }
   if (g_dbg_resid) g.p[0].resid = g_dbg_resid;
   if (g_dbg_cstat) g.p[0].cstat = g_dbg_cstat;
-  return launch_group(g, tile, s);
+  return launch_group(g, tile, g_tune, s);
 }
 
 int porl_adam_ema(float* p, const float* g, float* m, float* v, float* target, int64_t n, double lr, int32_t step,
@@ -1490,43 +1524,11 @@ int porl_per_sample(const double* tree, int64_t capacity, const double* u, int32
   return PORL_OK;
 }
 
-int porl_tune_set(const char* key, int value) {
-  if (!key) PORL_FAIL(PORL_ERR_INVALID, "null key");
-  if (!strcmp(key, "gemm_lds_pad")) { gemm_lds_pad() = std::max(0, value); return PORL_OK; }
-  if (!strcmp(key, "gemm_lds_pad_min_blocks")) { gemm_lds_pad_min_blocks() = std::max(0, value); return PORL_OK; }
-  if (!strcmp(key, "iql_pad_value")) { g_iql_pad_value = std::max(0, value); return PORL_OK; }
-  if (!strcmp(key, "iql_pad_policy")) { g_iql_pad_policy = std::max(0, value); return PORL_OK; }
-  if (!strcmp(key, "iql_pad_min_blocks")) { g_iql_pad_min_blocks = std::max(0, value); return PORL_OK; }
-  if (!strcmp(key, "iql_pad_min_k")) { g_iql_pad_min_k = std::max(0, value); return PORL_OK; }
-  if (!strcmp(key, "qnet_fused")) { g_qnet_fused = value != 0; return PORL_OK; }
-  if (!strcmp(key, "qnet_two_groups")) { g_qnet_two_groups = value != 0; return PORL_OK; }
-  if (!strcmp(key, "qnet_wgrad_share")) { g_qnet_wgrad_share = std::max(1, std::min(value, 16)); return PORL_OK; }
-  if (!strcmp(key, "qnet_rows16")) { g_qnet_rows16 = value != 0; return PORL_OK; }
-  if (!strcmp(key, "enc_dense_patch")) { g_enc_dense_patch = value != 0; return PORL_OK; }
-  if (!strcmp(key, "enc_s2d")) { g_enc_s2d = value != 0; return PORL_OK; }
-  if (!strcmp(key, "enc_patch_rows")) { g_enc_patch_rows = std::max(0, value); return PORL_OK; }
-  if (!strcmp(key, "enc_gemm_sb")) { g_enc_gemm_sb = value; return PORL_OK; }
-  if (!strcmp(key, "enc_tile_n96")) { g_enc_tile_n96 = value != 0; return PORL_OK; }
-  if (!strcmp(key, "enc_bn_sweep")) { g_enc_bn_sweep = value != 0; return PORL_OK; }
-  if (!strcmp(key, "enc_pconv_mfma")) { g_enc_pconv_mfma = value != 0; return PORL_OK; }
-  if (!strcmp(key, "enc_bf16_operands_only")) { g_enc_bf16_operands_only = value != 0; return PORL_OK; }
-  if (!strcmp(key, "iql_fold")) { g_iql_fold = value != 0; return PORL_OK; }
-  if (!strcmp(key, "skinny")) { g_skinny = value == 1 ? 7 : value; return PORL_OK; }
-  if (!strcmp(key, "skinny_pipelined")) { g_skinny_pipelined = value == 1 ? 7 : value; return PORL_OK; }     // -1: by width
-  if (!strcmp(key, "skinny_pipelined_max_h")) { g_skinny_pipelined_max_h = value; return PORL_OK; }
-  if (!strcmp(key, "dw0_slabs")) { g_dw0_slabs = std::max(1, std::min(value, SK_MAX)); return PORL_OK; }
-  if (!strcmp(key, "l0_tile")) { g_l0_tile = value; return PORL_OK; }
-  if (!strcmp(key, "l0_kernel")) { g_l0_kernel = value != 0; return PORL_OK; }
-  if (!strcmp(key, "vbwd_tile_short")) { g_vbwd_tile_short = value; return PORL_OK; }
-  if (!strncmp(key, "tile_map_short", 14) && key[14] >= '0' && key[14] <= '3' && !key[15] && value >= 0 && value < TILE_COUNT) {
-    g_tile_map_short[key[14] - '0'] = value;
-    return PORL_OK;
-  }
-  if (!strncmp(key, "tile_map", 8) && key[8] >= '0' && key[8] <= '3' && !key[9] && value >= 0 && value < TILE_COUNT) {
-    g_tile_map[key[8] - '0'] = value;
-    return PORL_OK;
-  }
-  PORL_FAIL(PORL_ERR_INVALID, "unknown tuning key '%s'", key);
+int porl_tune_set(const char* key, int value) { return tune_apply(g_tune, key, value); }
+
+int porl_iql_tune_set(porl_iql* h, const char* key, int value) {
+  if (!h) PORL_FAIL(PORL_ERR_INVALID, "null engine");
+  return tune_apply(h->tune, key, value);
 }
 
 // ---- stream signals: cross-stream ordering by 64-bit counters in signal memory ----------------------------------------
@@ -1689,6 +1691,7 @@ struct porl_qnet {
   int64_t fslab_stride = 0;
   bool fslab_clean = false;          // alignment gaps of the flat layout are never written: zeroed once
   bool slab_clean = false;           // same for the split-K slabs of the multi-launch path
+  Tune tune = g_tune;                // kernel selection: the process defaults at creation
 };
 
 
@@ -1801,7 +1804,7 @@ int porl_qnet_tensor_info(const porl_qnet* h, int index, int64_t* offset, int32_
   return PORL_OK;
 }
 int64_t porl_qnet_workspace_floats(const porl_qnet* h) { return h ? h->ws.total : 0; }
-int32_t porl_qnet_one_launch(const porl_qnet* h) { return h && h->fused_ok && g_qnet_fused ? 1 : 0; }
+int32_t porl_qnet_one_launch(const porl_qnet* h) { return h && h->fused_ok && h->tune.qnet_fused ? 1 : 0; }
 
 int porl_qnet_bind(porl_qnet* h, const porl_qnet_buffers* b) {
   if (!h || !b) PORL_FAIL(PORL_ERR_INVALID, "null argument");
@@ -1820,7 +1823,6 @@ int porl_qnet_bind(porl_qnet* h, const porl_qnet_buffers* b) {
 }
 
 static int qnet_ready(const porl_qnet* h, bool need_batch) {
-  g_short_blocks = false;
   if (!h) PORL_FAIL(PORL_ERR_INVALID, "null engine");
   if (!h->bound) PORL_FAIL(PORL_ERR_UNBOUND, "porl_qnet_bind() has not been called");
   if (need_batch && h->batch <= 0) PORL_FAIL(PORL_ERR_INVALID, "no minibatch loaded (porl_qnet_load_batch)");
@@ -1873,7 +1875,7 @@ static int qnet_forward(porl_qnet* h, int nnets, const float* const* params, con
       p.act = l < L ? ACT_RELU : ACT_NONE;
       g.p[k] = p;
     }
-    PORL_TRY(launch_group(g, pick_tile(g), s));
+    PORL_TRY(launch_group(g, pick_tile(g, h->tune), h->tune, s));
   }
   return PORL_OK;
 }
@@ -1912,14 +1914,14 @@ static int qnet_fused_backward(porl_qnet* h, const porl_qnet_hyper* hp, int B, c
     attr_set = true;
   }
   // 16 rows per block while 32-row blocks would leave CUs idle (config 3 at B = 4096: 128 blocks on 256 CUs)
-  const bool two = g_qnet_two_groups && h->fused2_lds_w2 > 0;
+  const bool two = h->tune.qnet_two_groups && h->fused2_lds_w2 > 0;
   if (samp && samp->n_rows > 0) {
     if (!two) PORL_FAIL(PORL_ERR_UNSUPPORTED, "in-kernel sampling needs the two-group step kernel");
     a.samp_n = samp->n_rows; a.samp_seed = samp->seed; a.samp_step = samp->step; a.samp_hb = feistel_half_bits(samp->n_rows);
     a.idx = nullptr;
   }
-  const bool rows16 = two && g_qnet_rows16 && h->fused16_lds_w2 > 0 && cdiv(B, QF_ROWS) < NUM_CU;
-  a.wgrad_share = g_qnet_wgrad_share;
+  const bool rows16 = two && h->tune.qnet_rows16 && h->fused16_lds_w2 > 0 && cdiv(B, QF_ROWS) < NUM_CU;
+  a.wgrad_share = h->tune.qnet_wgrad_share;
   const int nblk = cdiv(B, rows16 ? 16 : QF_ROWS);
   if (rows16) {
     const QnetFusedArgs& f16 = h->fargs16;
@@ -1998,7 +2000,7 @@ static int qnet_backward_chain(porl_qnet* h, float* dz, int B, hipStream_t s) {
       add_reduce(red, G + h->net.w[l], slabW, per, per, sk);
       add_reduce(red, G + h->net.b[l], slabC, out_d, out_d, sk);
     }
-    PORL_TRY(launch_group(g, tile, s));
+    PORL_TRY(launch_group(g, tile, h->tune, s));
     if (red.njobs == 8 || l == 0) { PORL_TRY(launch_reduce(red, s)); red = ReduceArgs{}; }
     dz = dz_next;
   }
@@ -2015,7 +2017,7 @@ int porl_qnet_cql_backward(porl_qnet* h, const porl_qnet_hyper* hp, void* stream
   hipStream_t s = (hipStream_t)stream;
   const int B = h->batch;
   float* W = h->buf.workspace;
-  if (h->fused_ok && g_qnet_fused)
+  if (h->fused_ok && h->tune.qnet_fused)
     return qnet_fused_backward(h, hp, B, W + h->ws.xs, h->Sp, W + h->ws.xn, h->Sp,
                                reinterpret_cast<const int64_t*>(W + h->ws.actions), W + h->ws.rew, W + h->ws.done, nullptr, s);
   return qnet_general_backward(h, hp, nullptr, s);
@@ -2262,7 +2264,7 @@ int porl_qnet_apply(porl_qnet* h, const porl_qnet_hyper* hp, void* stream) {
 int porl_qnet_learn(porl_qnet* h, const porl_qnet_hyper* hp, void* stream) {
   PORL_TRY(qnet_ready(h, true)); DevGuard _dg(h->device);
   if (!hp) PORL_FAIL(PORL_ERR_INVALID, "null hyper-parameters");
-  if (h->fused_ok && g_qnet_fused) {
+  if (h->fused_ok && h->tune.qnet_fused) {
     float* W = h->buf.workspace;
     return qnet_fused_backward(h, hp, h->batch, W + h->ws.xs, h->Sp, W + h->ws.xn, h->Sp,
                                reinterpret_cast<const int64_t*>(W + h->ws.actions), W + h->ws.rew, W + h->ws.done, nullptr,
@@ -2299,14 +2301,14 @@ int porl_qnet_learn_indexed(porl_qnet* h, const float* states, int64_t s_rs, con
   PORL_TRY(qnet_ready(h, false)); DevGuard _dg(h->device);
   if (!hp || !states || !actions || !rewards || !next_states || !dones) PORL_FAIL(PORL_ERR_INVALID, "null argument");
   if (batch < 1 || batch > h->cfg.max_batch) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", batch, h->cfg.max_batch);
-  if (!h->fused_ok || !g_qnet_fused)
+  if (!h->fused_ok || !h->tune.qnet_fused)
     return qnet_general_learn(h, hp, nullptr, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, idx, (hipStream_t)stream);
   return qnet_fused_backward(h, hp, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, idx,
                              (hipStream_t)stream, true);
 }
 
 int32_t porl_qnet_can_sample(const porl_qnet* h) {
-  return h && h->fused_ok && g_qnet_fused && g_qnet_two_groups && h->fused2_lds_w2 > 0 ? 1 : 0;
+  return h && h->fused_ok && h->tune.qnet_fused && h->tune.qnet_two_groups && h->fused2_lds_w2 > 0 ? 1 : 0;
 }
 
 int porl_qnet_learn_sampled(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
@@ -2329,7 +2331,7 @@ int porl_qnet_learn_variant(porl_qnet* h, const float* states, int64_t s_rs, con
   PORL_TRY(qnet_ready(h, false)); DevGuard _dg(h->device);
   if (!hp || !states || !actions || !rewards || !next_states || !dones || !variant) PORL_FAIL(PORL_ERR_INVALID, "null argument");
   if (batch < 1 || batch > h->cfg.max_batch) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", batch, h->cfg.max_batch);
-  if (!h->fused_ok || !g_qnet_fused)      // wide networks (a layer > 128 wide, > 5 Linear layers): the multi-launch path
+  if (!h->fused_ok || !h->tune.qnet_fused)      // wide networks (a layer > 128 wide, > 5 Linear layers): the multi-launch path
     return qnet_general_learn(h, hp, variant, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, idx, (hipStream_t)stream);
   return qnet_fused_backward(h, hp, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, idx,
                              (hipStream_t)stream, true, variant);

@@ -123,6 +123,10 @@ class IqlEngine:
             N.check(self._lib.porl_iql_set_mode(self._h, int(mode)), "porl_iql_set_mode")
             self._mode = mode
 
+    def tune_set(self, key, value):
+        """porl_tune_set for this engine only (it copied the process defaults when it was created)."""
+        N.check(self._lib.porl_iql_tune_set(self._h, key.encode(), int(value)), "porl_iql_tune_set")
+
     # -- memory ------------------------------------------------------------------------------------
     # Flat groups are allocated a little longer than the C library needs (zero tail) so that they split into equal,
     # 16-byte-aligned slices for every data-parallel world size that divides 840 (1..8, 10, 12, ...): the
@@ -419,4 +423,5 @@ def prof_read(max_entries=64):
 
 
 def tune_set(key, value):
+    """Process defaults (porl_tune_set): engines created afterwards copy them; IqlEngine.tune_set edits a live one."""
     N.check(N.lib().porl_tune_set(key.encode(), int(value)), "porl_tune_set")

@@ -104,6 +104,9 @@ int main() {
     REJECT(porl_iql_update_pipelined(h, &hp, 32, x, 124, (int64_t)1 << 41, 2, 0, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2));         // n_rows > 2^40
     REJECT(porl_iql_update_pipelined(h, nullptr, 32, x, 124, 1000, 2, 0, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2));
   }
+  REJECT(porl_iql_tune_set(h, "no_such_key", 1));
+  REJECT(porl_iql_tune_set(h, nullptr, 1));
+  ACCEPT(porl_iql_tune_set(h, "skinny", 0));
   porl_iql_destroy(h);
   porl_iql_destroy(nullptr);
   // ---- stateless building blocks ------------------------------------------------------------------------------------------
@@ -148,6 +151,7 @@ int main() {
   REJECT(porl_tune_set(nullptr, 1));
   REJECT(porl_tune_set("no_such_key", 1));
   ACCEPT(porl_tune_set("skinny", 7));
+  REJECT(porl_iql_tune_set(nullptr, "skinny", 0));
   REJECT(porl_tune_set_ptr("no_such_key", nullptr));
   REJECT(porl_signal_write(nullptr, 1, nullptr));
   REJECT(porl_signal_wait_ge(nullptr, 1, nullptr));

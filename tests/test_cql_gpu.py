@@ -152,19 +152,19 @@ def test_one_launch_gradients_on_odd_shapes(S, A, B, hidden):
     widths that are not multiples of 32, the widest supported network, and a single-row batch."""
     from porl_amd import engine as E
     from porl_amd.train.cql_trainer import QnetEngine
-    rng = np.random.default_rng(S * 1000 + A)
-    eng = QnetEngine(S, A, hidden, max(B, 64), DEV)
-    assert eng.fused
-    for flat in (eng.params, eng.params_tgt):           # through the parameter views: the images' padding stays zero
-        for v in eng.views(flat):
-            v.copy_(torch.from_numpy(rng.uniform(-0.3, 0.3, tuple(v.shape)).astype(np.float32)))
     st, ac, rw, ns, dn = make_discrete_transitions(B, S, A, seed=8)
     dev = lambda x: torch.from_numpy(x).to(DEV)
-    hp = eng.hyper(0.99, 0.7, 1.0 / B, 1, 5e-4)
     out = []
     for fused in (1, 0):
         try:
             E.tune_set("qnet_fused", fused)
+            eng = QnetEngine(S, A, hidden, max(B, 64), DEV)
+            assert eng.fused == bool(fused)
+            rng = np.random.default_rng(S * 1000 + A)
+            for flat in (eng.params, eng.params_tgt):   # through the parameter views: the images' padding stays zero
+                for v in eng.views(flat):
+                    v.copy_(torch.from_numpy(rng.uniform(-0.3, 0.3, tuple(v.shape)).astype(np.float32)))
+            hp = eng.hyper(0.99, 0.7, 1.0 / B, 1, 5e-4)
             eng.load_batch(dev(st), dev(ac), dev(rw), dev(ns), dev(dn))
             eng.grads.zero_()
             eng.cql_backward(hp)

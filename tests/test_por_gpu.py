@@ -349,8 +349,8 @@ def test_por_global_batch_of_config4_on_one_gpu():
 
 @pytest.fixture(params=[0, 7], ids=["gemm-path", "skinny-path"])
 def same_kernels_in_both_modes(request):
-    """The pipelined update and the one-stream update pick their <= 64-wide products' kernels separately (csrc: g_skinny /
-    g_skinny_pipelined — by default skinny.hpp on one stream, the grouped GEMM in the pipelined update, where it measured
+    """The pipelined update and the one-stream update pick their <= 64-wide products' kernels separately (csrc: Tune::skinny /
+    Tune::skinny_pipelined — by default skinny.hpp on one stream, the grouped GEMM in the pipelined update, where it measured
     faster).  "Pipelining only reorders" is a statement about equal kernels, so these tests pin one selection for both
     modes — each of the two; across selections results agree to rounding (test_skinny_kernels_agree_...)."""
     from porl_amd import engine as E
@@ -541,6 +541,33 @@ def test_input_layer_kernel_is_bit_identical_to_the_grouped_gemm(S, H, B):
         assert torch.equal(x, y)
 
 
+def test_tune_set_does_not_reach_an_engine_that_already_exists():
+    """porl_tune_set edits the process defaults, which an engine copies when it is created: a key set while an agent
+    is training does not change that agent's kernels.  B is built like A, then "skinny" is switched off (the grouped-
+    GEMM path, other summation order) before B trains: B still reproduces A bit for bit."""
+    from porl_amd import engine as E
+    S, H, L, B = 60, 256, 2, 256
+    rows = torch.from_numpy(make_rows(3 * B, S, 2, seed=41)).to(DEV)
+
+    def train(agent):
+        losses = []
+        for k in range(3):
+            s, r, sp, d, _ = split_rows(rows[k * B:(k + 1) * B], S, 2)
+            losses.append(agent.por_residual_update(s, sp, r, d))
+        return losses, [v.clone() for v in agent.state_dict().values()]
+
+    want = train(_make_por(S, H, L, B))
+    agent_b = _make_por(S, H, L, B)
+    try:
+        E.tune_set("skinny", 0)
+        got = train(agent_b)
+    finally:
+        E.tune_set("skinny", 7)
+    assert got[0] == want[0]
+    for x, y in zip(got[1], want[1]):
+        assert torch.equal(x, y)
+
+
 def test_one_call_pipelined_update_rejects_bad_arguments_without_side_effects():
     """porl_iql_update_pipelined (the small-network fast path of update_from_replay) validates the minibatch before it
     enqueues anything: an oversized batch raises, the step counters stay where they were, and the agent goes on to
@@ -617,7 +644,6 @@ def test_skinny_kernels_agree_with_the_grouped_gemm_path(S, H, L, B, sorl):
     row tiles (several tiles per slab) and SORL's 2-wide output layer; both paths are pinned to the reference by the
     golden tests above.  (Whole trajectories are NOT compared: Adam's first steps turn a 1e-10 gradient difference on
     a |g| ~ 1e-8 entry into a 1e-6 parameter difference, and ReLU-mask flips do the rest.)"""
-    from porl_amd import engine as E
     from porl_amd.agent.sorl import SORL
     from porl_amd.engine import IqlEngine
     A = 2
@@ -630,25 +656,22 @@ def test_skinny_kernels_agree_with_the_grouped_gemm_path(S, H, L, B, sorl):
         agent = _make_por(S, H, L, B)
         v_opt, p_opt, sched = agent.v_optimizer, agent.goal_policy_optimizer, agent.goal_lr_schedule
     eng = agent._engine
-    try:
-        for k in range(3):
-            s, r, sp, d, a = split_rows(rows[k * B:(k + 1) * B], S, A)
-            Bk = eng.load_batch(s, sp, r, d, a if sorl else sp)
-            v_opt.step_count += 1
-            p_opt.step_count += 1
-            hp = agent._hyper(Bk, v_opt, p_opt)
-            for phase, group, apply in (("value_backward", 0, "value_apply"), ("policy_backward", 1, "policy_apply")):
-                got = {}
-                for skinny in (0, 1):
-                    E.tune_set("skinny", skinny)
-                    getattr(eng, phase)(hp)
-                    flat = eng.grads_vf if group == 0 else eng.grads_pol
-                    got[skinny] = ([g.clone() for g in IqlEngine.views(flat, eng.tensor_table(group))], eng.stats[:3].clone())
-                for i, (g0, g1) in enumerate(zip(got[0][0], got[1][0])):
-                    scale = float(g0.abs().max())
-                    assert float((g0 - g1).abs().max()) <= 1e-6 * scale + 1e-12, (k, phase, i, scale)
-                np.testing.assert_allclose(got[1][1].cpu().numpy(), got[0][1].cpu().numpy(), rtol=1e-6)
-                getattr(eng, apply)(hp)
-            sched.step()
-    finally:
-        E.tune_set("skinny", 1)
+    for k in range(3):
+        s, r, sp, d, a = split_rows(rows[k * B:(k + 1) * B], S, A)
+        Bk = eng.load_batch(s, sp, r, d, a if sorl else sp)
+        v_opt.step_count += 1
+        p_opt.step_count += 1
+        hp = agent._hyper(Bk, v_opt, p_opt)
+        for phase, group, apply in (("value_backward", 0, "value_apply"), ("policy_backward", 1, "policy_apply")):
+            got = {}
+            for skinny in (0, 1):
+                eng.tune_set("skinny", skinny)
+                getattr(eng, phase)(hp)
+                flat = eng.grads_vf if group == 0 else eng.grads_pol
+                got[skinny] = ([g.clone() for g in IqlEngine.views(flat, eng.tensor_table(group))], eng.stats[:3].clone())
+            for i, (g0, g1) in enumerate(zip(got[0][0], got[1][0])):
+                scale = float(g0.abs().max())
+                assert float((g0 - g1).abs().max()) <= 1e-6 * scale + 1e-12, (k, phase, i, scale)
+            np.testing.assert_allclose(got[1][1].cpu().numpy(), got[0][1].cpu().numpy(), rtol=1e-6)
+            getattr(eng, apply)(hp)
+        sched.step()
