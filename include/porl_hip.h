@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define PORL_ABI_VERSION 6
+#define PORL_ABI_VERSION 7
 #define PORL_MAX_HIDDEN 8
 
 #define PORL_OK 0
@@ -331,6 +331,54 @@ int porl_qnet_forward(porl_qnet* h, int which, const float* states, int64_t s_rs
 /* compute_cql_penalty(states, actions) -> out[0] (device float) */
 int porl_qnet_penalty(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions,
                       int64_t a_rs, int32_t batch, float* out, void* stream);
+
+/* Online loop (src/porl/train/dqn_trainer.py:119-180): one launch per recorded transition, one per greedy action.
+ *
+ * porl_qnet_record: replay_buffer.push(state, action, reward, next_state, done) into slot `slot` of a device replay
+ * mirror (the five arrays of buffer/replay_buffer.py; states rows of state_dim floats, actions int64).  The transition
+ * is copied into the kernel's arguments at launch, so `state` / `next_state` (host, state_dim floats each) may be
+ * reused as soon as the call returns.  state_dim <= PORL_RECORD_MAX_STATE, else PORL_ERR_UNSUPPORTED. */
+#define PORL_RECORD_MAX_STATE 480
+typedef struct porl_qnet_mirror {
+  float* states;
+  float* next_states;
+  int64_t* actions;
+  float* rewards;
+  float* dones;
+  int64_t capacity;                  /* rows of each array */
+} porl_qnet_mirror;
+int porl_qnet_record(porl_qnet* h, int64_t slot, const float* state, const float* next_state, int64_t action,
+                     float reward, float done, const porl_qnet_mirror* mirror, void* stream);
+
+/* porl_qnet_act: argmax_a Q(s_b, a) for batch (1..8) states with the online (which 0) or target (1) parameters, in
+ * one workgroup.  States: rows [row, row + batch) of a device array of n_rows rows (row stride s_rs), or, when
+ * `states` is NULL, batch x state_dim floats of host memory `inline_states` (<= 256 floats) copied into the kernel's
+ * arguments.  Epilogue: kind 0 argmax over the n_actions outputs; 1 C51, outputs (n_act, n_sub) logits, argmax of
+ * sum_i softmax(logits)_i support[i]; 2 QR, outputs (n_act, n_sub) quantiles, argmax of their mean.  Ties go to the
+ * lowest index (torch.argmax).  `out` = a 16-word record in device or pinned host memory: int32 actions at [0, batch),
+ * at [8, 8 + n_stats) fp32 copies of stats[0, n_stats) (NULL stats: the engine's own loss statistics, n_stats <= 3)
+ * taken in stream order, i.e. after the step launched before.
+ * porl_qnet_act_ok: 1 when the network suits one workgroup (every layer <= 1024 wide and <= 2^19 padded parameter
+ * floats, i.e. <= 2 MiB streamed by one CU), else 0 and porl_qnet_act returns PORL_ERR_INVALID. */
+typedef struct porl_qnet_act_src {
+  int32_t batch;
+  const float* states;
+  int64_t s_rs;
+  int64_t row;
+  int64_t n_rows;
+  const float* inline_states;
+} porl_qnet_act_src;
+typedef struct porl_qnet_act_epilogue {
+  int32_t kind;
+  int32_t n_act;
+  int32_t n_sub;
+  const float* support;
+  const float* stats;
+  int32_t n_stats;
+} porl_qnet_act_epilogue;
+int32_t porl_qnet_act_ok(const porl_qnet* h);
+int porl_qnet_act(porl_qnet* h, int which, const porl_qnet_act_src* src, const porl_qnet_act_epilogue* epi,
+                  int32_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Building blocks, exported for tests, the replay buffer and other trainers

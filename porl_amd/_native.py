@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libporl_hip.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # every symbol include/porl_hip.h declares (tests check the .so exports exactly these)
 SYMBOLS = [
@@ -28,6 +28,7 @@ SYMBOLS = [
     "porl_qnet_tensor_info", "porl_qnet_workspace_floats", "porl_qnet_bind", "porl_qnet_load_batch",
     "porl_qnet_cql_backward", "porl_qnet_apply", "porl_qnet_learn", "porl_qnet_sync_target",
     "porl_qnet_forward", "porl_qnet_forward_loaded", "porl_qnet_backward", "porl_qr_loss", "porl_iqn_quantile_huber", "porl_iqn_cos_embed", "porl_iqn_hadamard", "porl_iqn_hadamard_backward", "porl_iqn_select", "porl_iqn_scatter", "porl_iqn_target", "porl_grad_clip", "porl_c51_loss", "porl_reduce_mean", "porl_qnet_penalty", "porl_qnet_learn_indexed", "porl_qnet_one_launch", "porl_qnet_learn_variant", "porl_qnet_can_sample", "porl_qnet_learn_sampled",
+    "porl_qnet_record", "porl_qnet_act_ok", "porl_qnet_act",
     "porl_enc_create", "porl_enc_destroy", "porl_enc_param_floats", "porl_enc_stat_floats",
     "porl_enc_workspace_floats", "porl_enc_tensors", "porl_enc_norms", "porl_enc_blocks",
     "porl_enc_tensor_info", "porl_enc_norm_info", "porl_enc_bind", "porl_enc_weights_changed", "porl_enc_forward",
@@ -70,6 +71,21 @@ class QnetHyper(C.Structure):
 class QnetVariant(C.Structure):
     _fields_ = [("double_dqn", C.c_int32), ("is_weights", C.c_void_p), ("uniform_weight", C.c_void_p),
                 ("td_abs", C.c_void_p), ("next_mask", C.c_void_p), ("td_off", C.c_int32)]
+
+
+class QnetMirror(C.Structure):
+    _fields_ = [("states", C.c_void_p), ("next_states", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p),
+                ("dones", C.c_void_p), ("capacity", C.c_int64)]
+
+
+class QnetActSrc(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("states", C.c_void_p), ("s_rs", C.c_int64), ("row", C.c_int64),
+                ("n_rows", C.c_int64), ("inline_states", C.c_void_p)]
+
+
+class QnetActEpilogue(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_act", C.c_int32), ("n_sub", C.c_int32), ("support", C.c_void_p),
+                ("stats", C.c_void_p), ("n_stats", C.c_int32)]
 
 
 class EncCfg(C.Structure):
@@ -174,6 +190,10 @@ def _declare(lib):
     lib.porl_iqn_target.argtypes = [vp, vp, vp, vp, f32, i32, i32, i32, vp, vp, vp]
     lib.porl_grad_clip.argtypes = [vp, i64, f32, vp, vp, vp]
     lib.porl_qnet_penalty.argtypes = [vp, vp, i64, vp, i64, i32, vp, vp]
+    lib.porl_qnet_record.argtypes = [vp, i64, vp, vp, i64, f32, f32, C.POINTER(QnetMirror), vp]
+    lib.porl_qnet_act_ok.argtypes = [vp]
+    lib.porl_qnet_act_ok.restype = i32
+    lib.porl_qnet_act.argtypes = [vp, C.c_int, C.POINTER(QnetActSrc), C.POINTER(QnetActEpilogue), vp, vp]
     lib.porl_enc_create.argtypes = [C.POINTER(EncCfg), C.POINTER(vp)]
     lib.porl_enc_destroy.argtypes = [vp]
     lib.porl_enc_destroy.restype = None

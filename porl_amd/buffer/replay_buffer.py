@@ -50,6 +50,37 @@ class ReplayBuffer:
     def __len__(self) -> int:
         return self.size
 
+    def record(self, state, action, reward, next_state, done, engine=None) -> bool:
+        """`push` plus the same row written into the device mirror by one launch (porl_qnet_record through `engine`, a
+        QnetEngine on this buffer's device), instead of queueing the slot for the next `_sync_mirror`.  Creates the
+        mirror when there is none.  Returns True when the mirror row was written now; False when the state is too wide
+        for the kernel's arguments and the row took `push`'s deferred path.  Without `engine` a minimal engine of the
+        buffer's state width is made once."""
+        from ..train.cql_trainer import QnetEngine
+        p = self.position
+        S = self._flat_states(self.states).shape[1]
+        if S > QnetEngine.RECORD_MAX_STATE:
+            self.push(state, action, reward, next_state, done)
+            return False
+        if engine is None:
+            if getattr(self, "_rec_engine", None) is None:    # a minimal engine of this state width: the handle the call needs
+                self._rec_engine = QnetEngine(S, 1, [1], 1, self.device)
+                self._rec_engine._ensure_bound()
+            engine = self._rec_engine
+        self.states[p] = state
+        self.actions[p] = action
+        self.rewards[p] = reward
+        self.next_states[p] = next_state
+        self.dones[p] = float(done)
+        self.position = (p + 1) % self.capacity
+        self.size = min(self.size + 1, self.capacity)
+        if self._mirror is None:
+            self._sync_mirror()                          # the new mirror copies every host row, this one included
+        else:
+            engine.record(self._mirror, p, self._flat_states(self.states)[p], self._flat_states(self.next_states)[p],
+                          self.actions[p], self.rewards[p], self.dones[p])
+        return True
+
     # -- device mirror ----------------------------------------------------------------------------
     def _flat_states(self, arr):
         return arr.reshape(self.capacity, -1)

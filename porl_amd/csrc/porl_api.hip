@@ -20,6 +20,7 @@
 #include "qnet_fused.hpp"
 #include "per_tree.hpp"
 #include "dist_losses.hpp"
+#include "online.hpp"
 
 using namespace porl;
 
@@ -1692,6 +1693,8 @@ struct porl_qnet {
   bool fslab_clean = false;          // alignment gaps of the flat layout are never written: zeroed once
   bool slab_clean = false;           // same for the split-K slabs of the multi-launch path
   Tune tune = g_tune;                // kernel selection: the process defaults at creation
+  const void* act_out_host = nullptr;  // porl_qnet_act: last record pointer seen and its device address
+  int32_t* act_out_dev = nullptr;
 };
 
 
@@ -2397,6 +2400,100 @@ int porl_qnet_penalty(porl_qnet* h, const float* states, int64_t s_rs, const int
   PORL_HIP(hipGetLastError());
   PORL_HIP(hipMemcpyAsync(out, W + h->ws.part_td + 2, sizeof(float), hipMemcpyDeviceToDevice, s));
   (void)r;
+  return PORL_OK;
+}
+
+// ---- online loop: record / act (csrc/online.hpp) ----------------------------------------------------------------------
+int porl_qnet_record(porl_qnet* h, int64_t slot, const float* state, const float* next_state, int64_t action,
+                     float reward, float done, const porl_qnet_mirror* m, void* stream) {
+  PORL_TRY(qnet_ready(h, false)); DevGuard _dg(h->device);
+  if (!state || !next_state || !m || !m->states || !m->next_states || !m->actions || !m->rewards || !m->dones)
+    PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  const int S = h->cfg.state_dim;
+  if (S > ONL_MAX_RECORD_S) PORL_FAIL(PORL_ERR_UNSUPPORTED, "state_dim %d > %d: too wide for the kernel arguments", S, ONL_MAX_RECORD_S);
+  if (slot < 0 || slot >= m->capacity) PORL_FAIL(PORL_ERR_INVALID, "slot %lld outside [0,%lld)", (long long)slot, (long long)m->capacity);
+  OnlineRecordArgs a;
+  a.states = m->states; a.next_states = m->next_states; a.actions = m->actions; a.rewards = m->rewards; a.dones = m->dones;
+  a.slot = slot; a.action = action; a.reward = reward; a.done = done; a.S = S;
+  memcpy(a.x, state, sizeof(float) * S);
+  memcpy(a.x + S, next_state, sizeof(float) * S);
+  hipLaunchKernelGGL(online_record_kernel, dim3(1), dim3(S > 64 ? 256 : 64), 0, (hipStream_t)stream, a);
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+static bool qnet_act_fits(const porl_qnet* h) {
+  for (int l = 0; l <= h->cfg.n_hidden + 1; ++l)
+    if (h->net.dims[l] > ONL_MAX_W) return false;
+  return h->n_params <= (int64_t(1) << 19);
+}
+
+int32_t porl_qnet_act_ok(const porl_qnet* h) { return h && qnet_act_fits(h) ? 1 : 0; }
+
+int porl_qnet_act(porl_qnet* h, int which, const porl_qnet_act_src* src, const porl_qnet_act_epilogue* epi, int32_t* out,
+                  void* stream) {
+  PORL_TRY(qnet_ready(h, false)); DevGuard _dg(h->device);
+  if (!src || !epi || !out) PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  if (!qnet_act_fits(h))
+    PORL_FAIL(PORL_ERR_INVALID, "network too large for the one-workgroup act kernel (a layer > %d wide or > 2^19 parameter "
+              "floats); use porl_qnet_forward", ONL_MAX_W);
+  const int B = src->batch, S = h->cfg.state_dim, n_out = h->cfg.n_actions;
+  if (B < 1 || B > ONL_MAX_B) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", B, ONL_MAX_B);
+  OnlineActArgs a;
+  if (src->states) {
+    if (src->row < 0 || src->row + B > src->n_rows) PORL_FAIL(PORL_ERR_INVALID, "rows [%lld,%lld) outside the %lld-row array",
+                                                                (long long)src->row, (long long)(src->row + B), (long long)src->n_rows);
+    if (src->s_rs < S) PORL_FAIL(PORL_ERR_INVALID, "row stride %lld < state_dim %d", (long long)src->s_rs, S);
+    a.states = src->states + src->row * src->s_rs;
+    a.s_rs = src->s_rs;
+  } else {
+    if (!src->inline_states) PORL_FAIL(PORL_ERR_INVALID, "no state source");
+    if (B * S > ONL_MAX_INLINE) PORL_FAIL(PORL_ERR_INVALID, "inline states: %d x %d floats > %d", B, S, ONL_MAX_INLINE);
+    a.states = nullptr;
+    a.s_rs = S;
+    memcpy(a.x_inline, src->inline_states, sizeof(float) * B * S);
+  }
+  a.kind = epi->kind;
+  if (epi->kind == 0) {
+    a.n_act = n_out; a.n_sub = 1;
+  } else if (epi->kind == 1 || epi->kind == 2) {
+    if (epi->n_act < 1 || epi->n_sub < 1 || (int64_t)epi->n_act * epi->n_sub != n_out)
+      PORL_FAIL(PORL_ERR_INVALID, "epilogue (%d actions x %d) does not match the %d outputs", epi->n_act, epi->n_sub, n_out);
+    if (epi->kind == 1 && !epi->support) PORL_FAIL(PORL_ERR_INVALID, "C51 epilogue needs the support");
+    a.n_act = epi->n_act; a.n_sub = epi->n_sub;
+  } else {
+    PORL_FAIL(PORL_ERR_INVALID, "unknown epilogue kind %d", epi->kind);
+  }
+  a.support = epi->support;
+  if (epi->n_stats < 0 || epi->n_stats > 3) PORL_FAIL(PORL_ERR_INVALID, "n_stats %d outside [0,3]", epi->n_stats);
+  a.stats = epi->stats ? epi->stats : h->buf.stats;
+  a.n_stats = epi->n_stats;
+  // the record may be pinned host memory: the kernel stores through its device address
+  if (out != h->act_out_host) {
+    hipPointerAttribute_t pa;
+    if (hipPointerGetAttributes(&pa, out) != hipSuccess) {
+      (void)hipGetLastError();
+      PORL_FAIL(PORL_ERR_INVALID, "act record is neither device memory nor pinned host memory");
+    }
+    int32_t* dev = nullptr;
+    if (pa.type == hipMemoryTypeDevice) dev = out;
+    else if (pa.type == hipMemoryTypeHost && pa.devicePointer) dev = static_cast<int32_t*>(pa.devicePointer);
+    if (!dev) PORL_FAIL(PORL_ERR_INVALID, "act record is neither device memory nor pinned host memory");
+    h->act_out_host = out;
+    h->act_out_dev = dev;
+  }
+  a.out = h->act_out_dev;
+  a.params = which ? h->buf.params_tgt : h->buf.params;
+  const int L = h->cfg.n_hidden;
+  a.n_lin = L + 1;
+  int maxw = 0;
+  for (int l = 0; l <= L + 1; ++l) { a.dims[l] = h->net.dims[l]; maxw = std::max(maxw, h->net.dims[l]); }
+  for (int l = 0; l <= L; ++l) { a.w_off[l] = h->net.w[l]; a.b_off[l] = h->net.b[l]; a.wld[l] = h->wld[l]; }
+  a.B = B;
+  a.ldx = (int)ru4(maxw);
+  const size_t lds = sizeof(float) * 2 * B * a.ldx;          // <= 2 x 8 x 1024 floats = 64 KiB
+  hipLaunchKernelGGL(online_act_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, a);
+  PORL_HIP(hipGetLastError());
   return PORL_OK;
 }
 

@@ -45,3 +45,9 @@ class C51Trainer(DistTrainerBase):
             return int(np.random.randint(self.action_size))
         x = torch.from_numpy(np.asarray(state)).float().unsqueeze(0).to(self.device)
         return self._greedy(self.q_network.get_q_values(x))
+
+    _act_for = select_action
+    _online_threshold = "batch"
+
+    def _act_epilogue(self):
+        return 1, self.atom_size, self.support.float().contiguous()

@@ -188,6 +188,55 @@ class QnetEngine:
                                             self.cfg.n_actions, N.current_stream_ptr(self.device)), "porl_qnet_forward")
         return q
 
+    # -- online loop (csrc/online.hpp) ----------------------------------------------------------------
+    RECORD_MAX_STATE = 480          # PORL_RECORD_MAX_STATE: 2 x state_dim floats ride in the record kernel's arguments
+    ACT_MAX_BATCH = 8
+    ACT_MAX_INLINE = 256            # floats of inline states per act launch
+
+    def record(self, mirror, slot, state, next_state, action, reward, done):
+        """Write one transition (host float32 rows `state` / `next_state`) into row `slot` of a device replay mirror
+        (the dict of ReplayBuffer._mirror) with one launch; the values travel in the kernel's arguments."""
+        self._ensure_bound()
+        key = tuple(mirror[k].data_ptr() for k in ("states", "next_states", "actions", "rewards", "dones"))
+        if getattr(self, "_mirror_key", None) != key:
+            for k, dt in (("states", torch.float32), ("next_states", torch.float32), ("actions", torch.int64),
+                          ("rewards", torch.float32), ("dones", torch.float32)):
+                t = mirror[k]
+                if t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                    raise RuntimeError(f"mirror {k}: need a contiguous {dt} tensor on {self.device}")
+            if mirror["states"].shape[1:].numel() != self.cfg.state_dim or mirror["next_states"].shape != mirror["states"].shape:
+                raise RuntimeError("mirror rows do not match the engine's state_dim")
+            self._mirror_c = N.QnetMirror(*[C.c_void_p(p) for p in key], int(mirror["states"].shape[0]))
+            self._mirror_key = key
+        N.check(self._lib.porl_qnet_record(self._h, int(slot), state.ctypes.data, next_state.ctypes.data, int(action),
+                                           float(reward), float(done), C.byref(self._mirror_c),
+                                           N.current_stream_ptr(self.device)), "porl_qnet_record")
+
+    @property
+    def act_ok(self):
+        """True when the network suits the one-workgroup act kernel (every layer <= 1024 wide, <= 2^19 parameter floats)."""
+        return bool(self._lib.porl_qnet_act_ok(self._h))
+
+    def act(self, out, states=None, row=0, batch=1, inline=None, which=0, kind=0, n_act=0, n_sub=1, support=None,
+            stats=None, n_stats=0):
+        """Greedy action(s) in one launch (porl_qnet_act) into the int32 record `out` (16 words, device or pinned host):
+        out[:batch] = argmax_a Q(s_b, a) of rows [row, row + batch) of the device array `states`, or of `inline`
+        (host float32, batch x state_dim); out[8:8+n_stats] (as fp32) = stats[:n_stats] (None: the engine's statistics).
+        kind 0: argmax of the outputs; 1: C51 expectation over n_sub atoms with `support`; 2: QR mean of n_sub quantiles."""
+        self._ensure_bound()
+        if states is not None:
+            if states.dtype != torch.float32 or states.device != self.device or states.stride(-1) != 1:
+                raise RuntimeError(f"states: need float32 rows on {self.device}")
+            src = N.QnetActSrc(int(batch), states.data_ptr(), states.stride(0), int(row), states.shape[0], None)
+        else:
+            inline = np.ascontiguousarray(inline, dtype=np.float32)
+            src = N.QnetActSrc(int(batch), None, self.cfg.state_dim, 0, 0, inline.ctypes.data)
+        epi = N.QnetActEpilogue(int(kind), int(n_act), int(n_sub), None if support is None else support.data_ptr(),
+                                None if stats is None else stats.data_ptr(), int(n_stats))
+        N.check(self._lib.porl_qnet_act(self._h, int(which), C.byref(src), C.byref(epi), C.c_void_p(out.data_ptr()),
+                                        N.current_stream_ptr(self.device)), "porl_qnet_act")
+        return out
+
     def penalty(self, states, actions):
         self._ensure_bound()
         states = self._states(states)
@@ -313,12 +362,13 @@ class CQLTrainer:
     def __init__(self, state_size, action_size, gamma, epsilon=1.0, epsilon_min=0.05, epsilon_decay=0.99,
                  update_target_freq=10, device=torch.device("cpu"), network=QNetwork, log_dir="logs",
                  num_epochs=1000, threshold=0.1, alpha=1, learning_rate=0.0005, replay_buffer=None,
-                 batch_size=64, max_batch=4096):
+                 batch_size=64, max_batch=4096, transition_learning_step=10000):
         self.state_size, self.action_size = state_size, action_size
         self.device = torch.device(device)
         self.gamma, self.epsilon, self.epsilon_min, self.epsilon_decay = gamma, epsilon, epsilon_min, epsilon_decay
         self.learning_rate, self.update_target_freq = learning_rate, update_target_freq
         self.num_epochs, self.threshold, self.alpha = num_epochs, threshold, alpha
+        self.training_learning_step = transition_learning_step       # train_online's learn threshold (dqn_trainer.py:62)
         # same construction order / RNG consumption as dqn_trainer.py:66-70; `network` is any callable (state_size,
         # action_size) -> QNetwork, e.g. `lambda s, a: QNetwork(s, a, [256, 256])` for other hidden sizes
         self.q_network = network(state_size, action_size)
@@ -385,6 +435,21 @@ class CQLTrainer:
     def learn(self):
         return self.learn_on(*self.replay_buffer.sample(self.batch_size))
 
+    _rows_for = learn_on          # the learn_on that _learn_rows reproduces (a subclass overriding learn_on opts out)
+
+    def _learn_rows(self, idx):
+        """learn_on on rows `idx` (device int64) of the replay mirror, gathered inside the step kernel."""
+        eng, m = self._engine, self.replay_buffer._mirror
+        self.optimizer.step_count += 1
+        g = self.optimizer.param_groups[0]
+        hp = eng.hyper(self.gamma, float(self.alpha), 1.0 / idx.numel(), self.optimizer.step_count, g["lr"], g["betas"],
+                       g["eps"])
+        eng.learn_indexed(hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"], idx,
+                          variant=self._rows_variant())
+
+    def _rows_variant(self):
+        return None
+
     def learn_device_sampled(self, seed=0):
         """Extension (not in the reference): `learn()` with the B distinct indices drawn on the device (keyed
         permutation) instead of numpy's O(N) host permutation — no host work, no host->device copies."""
@@ -434,6 +499,18 @@ class CQLTrainer:
         self.logger.close()
         return losses
 
+    def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
+        """dqn_trainer.py:119-180 (train/online.py): learns once len(replay_buffer) >= training_learning_step; greedy
+        actions, pushes and learn steps take the one-launch forms when the network and buffer allow."""
+        from . import online
+        fast = None
+        cls = type(self)
+        if online.fast_ok(self) and cls._act_for is cls.select_action and cls._greedy_for is cls.get_action:
+            rows = cls.learn is CQLTrainer.learn and cls._rows_for is cls.learn_on and not self._exchange.active
+            fast = online._Fast(self, learn_rows=self._learn_rows if rows else None)
+        return online.run(self, env, policy, num_episodes, max_steps, self.training_learning_step, self.replay_buffer,
+                          self.replay_buffer.push, fast)
+
     # -- acting -----------------------------------------------------------------------------------
     def get_action(self, state: np.ndarray) -> int:
         x = torch.as_tensor(np.asarray(state), dtype=torch.float32, device=self.device).unsqueeze(0)
@@ -443,3 +520,16 @@ class CQLTrainer:
         if np.random.rand() < self.epsilon:
             return int(np.random.randint(self.action_size))
         return self.get_action(state)
+
+    _act_for, _greedy_for = select_action, get_action      # the action rule porl_qnet_act reproduces in train_online
+
+    def greedy_action(self, state: np.ndarray) -> int:
+        """get_action(state) in one launch (porl_qnet_act on the state carried in the kernel's arguments)."""
+        eng = self._engine
+        if not eng.act_ok or eng.cfg.state_dim > eng.ACT_MAX_INLINE:
+            return self.get_action(state)
+        if getattr(self, "_act_rec", None) is None:
+            self._act_rec = torch.zeros(16, dtype=torch.int32).pin_memory()
+        eng.act(self._act_rec, inline=np.asarray(state, dtype=np.float32).reshape(-1))
+        torch.cuda.current_stream(eng.device).synchronize()
+        return int(self._act_rec[0])

@@ -25,7 +25,8 @@ class DistTrainerBase:
     replay_buffer, batch_size, gamma, epsilon*, update_target_freq, device, logger."""
 
     def _setup(self, q_network, target_network, state_size, action_size, gamma, epsilon, epsilon_min, epsilon_decay,
-               update_target_freq, device, learning_rate, log_dir, batch_size, max_batch, replay_buffer):
+               update_target_freq, device, learning_rate, log_dir, batch_size, max_batch, replay_buffer,
+               transition_learning_step=10000):
         self.state_size, self.action_size = state_size, action_size
         self.device = torch.device(device)
         self.gamma, self.epsilon, self.epsilon_min, self.epsilon_decay = gamma, epsilon, epsilon_min, epsilon_decay
@@ -44,6 +45,7 @@ class DistTrainerBase:
         self.optimizer = _FlatAdam(eng, list(q_network.parameters()), learning_rate)
         self.replay_buffer = replay_buffer if replay_buffer is not None else ReplayBuffer(100000, (state_size,), self.device)
         self.batch_size = batch_size
+        self.training_learning_step = transition_learning_step     # train_online's learn threshold (dqn_trainer.py:62)
         self.logger = Logger(log_dir=log_dir)
         self.async_losses = False
         mb = eng.cfg.max_batch
@@ -99,3 +101,23 @@ class DistTrainerBase:
 
     def _greedy(self, q_values):
         return int(q_values.argmax(dim=1).item())
+
+    # -- online loop (train/online.py) --------------------------------------------------------------------------------
+    _online_threshold = "transition"   # dqn_trainer.py:148 (QR-DQN inherits it); C51 overrides: "batch" (c51_trainer.py:205)
+    _act_for = None                    # the subclass's select_action that _act_epilogue reproduces
+
+    def _act_epilogue(self):
+        """(kind, n_sub, support) of porl_qnet_act for this network's greedy rule."""
+        raise NotImplementedError
+
+    def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
+        """dqn_trainer.py:119-180 / c51_trainer.py:176-225; greedy actions and pushes take the one-launch forms when the
+        network fits the act kernel, learn() keeps its multi-launch form."""
+        from . import online
+        fast = None
+        if online.fast_ok(self) and type(self)._act_for is type(self).select_action:
+            kind, n_sub, support = self._act_epilogue()
+            fast = online._Fast(self, kind=kind, n_sub=n_sub, support=support)
+        threshold = self.batch_size if self._online_threshold == "batch" else self.training_learning_step
+        return online.run(self, env, policy, num_episodes, max_steps, threshold, self.replay_buffer,
+                          self.replay_buffer.push, fast)

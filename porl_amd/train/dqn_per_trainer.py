@@ -55,3 +55,10 @@ class PERTrainer(CQLTrainer):
             return eng.stats[:3]
         loss, self.last_td_loss, _ = eng.stats[:3].tolist()
         return loss
+
+    def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
+        """dqn_per_trainer.py:127-175: memory.add(max_initial_priority, ...) and a learn step once len(memory) >=
+        batch_size; the loop of train/online.py on this trainer's select_action / add / learn."""
+        from . import online
+        return online.run(self, env, policy, num_episodes, max_steps, self.batch_size, self.memory,
+                          lambda *e: self.memory.add(self.max_initial_priority, *e))

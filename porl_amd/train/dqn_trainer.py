@@ -45,3 +45,8 @@ class DDQNTrainer(DQNTrainer):
             return eng.stats[:3]
         loss, self.last_td_loss, _ = eng.stats[:3].tolist()
         return loss
+
+    _rows_for = learn_on
+
+    def _rows_variant(self):
+        return N.QnetVariant(1, None, None, None)

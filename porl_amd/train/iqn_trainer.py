@@ -95,7 +95,7 @@ class IQNTrainer:
                  batch_size: int = 64, kappa: float = 1.0, embedding_dim: int = 64, num_quantiles_k: int = 8,
                  num_quantiles_n_policy: int = 32, num_quantiles_n_prime_loss: int = 8,
                  num_quantiles_n_double_prime_loss: int = 8, dueling_network: bool = True, log_dir: str = "logs",
-                 hidden_size: int = 512, max_norm: float = 10.0, replay_buffer=None):
+                 hidden_size: int = 512, max_norm: float = 10.0, replay_buffer=None, transition_learning_step: int = 10000):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise N.NativeError("porl_amd computes on a HIP device only (device=%s); there is no CPU path" % self.device)
@@ -108,6 +108,7 @@ class IQNTrainer:
         self.num_quantiles_n_prime_loss = num_quantiles_n_prime_loss
         self.num_quantiles_n_double_prime_loss = num_quantiles_n_double_prime_loss
         self.max_norm = max_norm
+        self.training_learning_step = transition_learning_step       # train_online's learn threshold (dqn_trainer.py:62)
         self.q_network = IQNNetwork(state_size, action_size, embedding_dim, hidden_size).to(self.device)
         self.target_network = IQNNetwork(state_size, action_size, embedding_dim, hidden_size).to(self.device)
         self.optimizer = _FlatAdam(self.q_network, learning_rate)
@@ -181,9 +182,20 @@ class IQNTrainer:
         return loss
 
     def train_offline(self, policy=None, num_iterations: int = 10000):
+        """dqn_trainer.py:182-204 (inherited by the reference's IQNTrainer)."""
         losses = []
-        for step in range(num_iterations):
-            losses.append(self.learn() if policy is None else policy())
-            if step % self.update_target_freq == 0:
+        for self.training_step in range(num_iterations):
+            loss = self.learn() if policy is None else policy()
+            self.logger.log_loss(self.training_step, loss)
+            if self.training_step % self.update_target_freq == 0:
                 self.sync_target()
+            losses.append(loss)
+        self.logger.close()
         return losses
+
+    def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
+        """dqn_trainer.py:119-180 (inherited by the reference's IQNTrainer) on this trainer's select_action (it samples
+        its own quantile fractions), push and learn; learns once len(replay_buffer) >= training_learning_step."""
+        from . import online
+        return online.run(self, env, policy, num_episodes, max_steps, self.training_learning_step, self.replay_buffer,
+                          self.replay_buffer.push)

@@ -1,0 +1,203 @@
+"""`train_online` of the Q-learning trainers: the environment loop of src/porl/train/dqn_trainer.py:119-180
+(c51_trainer.py:176-225, dqn_per_trainer.py:127-175 differ only in the action rule, the memory and the learn threshold),
+statement for statement — the same env protocol (reset -> (state, info), step -> 5 values, done = done or truncated), the
+same order of draws from the global numpy stream (epsilon draw, randint when exploring, np.random.choice inside the
+sample), the same logger calls with the same values, per-episode epsilon decay and target sync.
+
+Fast path (`_Fast`), taken when the network lives on a QnetEngine and the memory is the device-mirrored ReplayBuffer:
+  * greedy action: porl_qnet_act — one launch on the state just recorded (a slot of the mirror's next_states) or, right
+    after env.reset(), on the state carried in the kernel's arguments; the action comes back in a pinned record, read
+    after one stream synchronisation;
+  * push: ReplayBuffer.record — one launch writes the row into the mirror (no _sync_mirror before the next sample);
+  * learn (plain / Double / dueling DQN and CQL on the one-launch step kernel): the sampled rows are gathered inside the
+    step kernel (learn_indexed); the only host->device copy is the minibatch's indices.  The loss is not read back at
+    once: the act record carries the statistics of the step before it, and losses of steps followed by an exploring
+    step are parked in a device log, read at the next greedy action or the episode's end.  The logger calls are
+    replayed then, in their original order.
+Everything else (PER, IQN, user `policy` callables, networks too large for one workgroup) runs the reference loop on
+the trainer's own select_action / push / learn.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+
+class _Fast:
+    def __init__(self, trainer, kind=0, n_sub=1, support=None, learn_rows=None):
+        self.t, self.eng, self.rb = trainer, trainer._engine, trainer.replay_buffer
+        self.kind, self.n_sub, self.support = kind, n_sub, support
+        self.n_act = trainer.action_size
+        self.learn_rows = learn_rows               # None: the trainer's own learn()
+        self.S = int(np.prod(self.rb.state_shape))
+        self.rec = torch.zeros(16, dtype=torch.int32).pin_memory()
+        self.rec_f = self.rec.view(torch.float32)
+        self.stream = torch.cuda.current_stream(self.eng.device)
+        self.state_row = None                      # mirror row holding the current state (None: pass it inline)
+        # deferred losses
+        self.calls = []                            # (method, args, loss slot or None)
+        self.log = None                            # device losses of learn steps followed by an exploring step
+        self.parked = []                           # their loss slots, in log order
+        self.in_stats = None                       # loss slot of the newest learn, its value still only in eng.stats
+        self.values = []                           # loss per slot (None until read)
+        # minibatch indices: pinned staging ring; a slot is rewritten only after its copy has completed
+        self.R = 32
+        B = trainer.batch_size
+        self.idx_host = torch.zeros(self.R, B, dtype=torch.int64).pin_memory()
+        self.idx_dev = torch.zeros(self.R, B, dtype=torch.int64, device=self.eng.device)
+        self.idx_ev = [None] * self.R
+        self.idx_k = 0
+
+    # -- acting / recording -------------------------------------------------------------------------------------------
+    def greedy(self, state):
+        eng = self.eng
+        n_stats = 1 if self.in_stats is not None else 0
+        kw = dict(kind=self.kind, n_act=self.n_act, n_sub=self.n_sub, support=self.support, n_stats=n_stats)
+        if self.state_row is not None:
+            eng.act(self.rec, states=self.rb._mirror["next_states"], row=self.state_row, **kw)
+        else:
+            eng.act(self.rec, inline=np.asarray(state, dtype=np.float32).reshape(-1), **kw)
+        self.stream.synchronize()
+        if n_stats:
+            self.resolve(float(self.rec_f[8]))
+        return int(self.rec[0])
+
+    def explore(self):
+        """An exploring step: park the newest loss (if any) before the next learn overwrites the statistics."""
+        if self.in_stats is not None:
+            n = len(self.parked)
+            self.log[n:n + 1].copy_(self.eng.stats[:1])
+            self.parked.append(self.in_stats)
+            self.in_stats = None
+
+    def push(self, state, action, reward, next_state, done):
+        p = self.rb.position
+        self.state_row = p if self.rb.record(state, action, reward, next_state, done, engine=self.eng) else None
+
+    # -- learning -----------------------------------------------------------------------------------------------------
+    def learn(self):
+        t = self.t
+        if self.learn_rows is None:
+            return t.learn()
+        idx = np.random.choice(self.rb.size, t.batch_size, replace=False)       # ReplayBuffer.sample's draw
+        self.rb._sync_mirror()
+        k = self.idx_k
+        self.idx_k = (k + 1) % self.R
+        if self.idx_ev[k] is not None:
+            self.idx_ev[k].synchronize()
+        else:
+            self.idx_ev[k] = torch.cuda.Event()
+        self.idx_host[k].numpy()[:] = idx
+        d = self.idx_dev[k]
+        d.copy_(self.idx_host[k], non_blocking=True)
+        self.idx_ev[k].record(self.stream)
+        self.learn_rows(d)
+        if t.async_losses:
+            return self.eng.stats[:3]
+        if self.log is None:
+            self.log = torch.zeros(self.max_steps + 1, dtype=torch.float32, device=self.eng.device)
+        self.values.append(None)
+        self.in_stats = len(self.values) - 1
+        return _Loss(len(self.values) - 1)
+
+    def resolve(self, newest=None):
+        """Read every outstanding loss (one readback at most) and replay the queued logger calls.  `newest`: the value
+        of the newest learn step's loss, already on the host (from the act record)."""
+        if newest is not None:
+            self.values[self.in_stats] = newest
+            self.in_stats = None
+        self.explore()
+        if self.parked:
+            for i, v in zip(self.parked, self.log[:len(self.parked)].tolist()):
+                self.values[i] = v
+        for fn, args in self.calls:
+            fn(*[self.values[a.i] if isinstance(a, _Loss) else a for a in args])
+        self.calls, self.values, self.parked = [], [], []
+
+    def log_call(self, fn, *args):
+        if self.calls or any(isinstance(a, _Loss) for a in args):
+            self.calls.append((fn, args))
+        else:
+            fn(*args)
+
+
+class _Loss:
+    __slots__ = ("i",)
+
+    def __init__(self, i):
+        self.i = i
+
+
+def run(trainer, env, policy, num_episodes, max_steps, threshold, memory, push, fast=None):
+    """dqn_trainer.py:119-180 with `memory` / `push` / the learn threshold of the trainer at hand; `fast` replaces the
+    action rule, push and learn by the one-launch forms (loop semantics unchanged)."""
+    t = trainer
+    if fast is not None:
+        fast.max_steps = max_steps
+        push = fast.push
+    rewards_history = []
+    for episode in range(num_episodes):
+        state, _ = env.reset()
+        episode_reward = 0
+        if fast is not None:
+            fast.state_row = None
+        for step in range(max_steps):
+            if fast is None:
+                action = t.select_action(state)
+            elif np.random.rand() < t.epsilon:
+                fast.explore()
+                action = np.random.randint(t.action_size)
+            else:
+                action = fast.greedy(state)
+            next_state, reward, done, truncated, _ = env.step(action)
+            done = done or truncated
+
+            push(state, action, reward, next_state, done)
+            state = next_state
+            episode_reward += reward
+
+            log = t.logger.log_step if fast is None else (lambda *a: fast.log_call(t.logger.log_step, *a))
+            log(episode, step, reward, None, t.epsilon)
+
+            if len(memory) >= threshold:
+                if policy is None:
+                    loss = t.learn() if fast is None else fast.learn()
+                else:
+                    loss = policy()
+                if t.logger is not None:
+                    log(episode, step, reward, loss, t.epsilon)
+
+            if done:
+                break
+
+        if fast is not None:
+            fast.resolve()
+        t.epsilon = max(t.epsilon_min, t.epsilon * t.epsilon_decay)
+        if episode % t.update_target_freq == 0:
+            t.sync_target()
+
+        t.logger.log_episode(episode)
+        rewards_history.append(episode_reward)
+
+        if episode % 10 == 0:
+            print(f"Episode {episode}, Reward: {episode_reward:.2f}, Epsilon: {t.epsilon:.3f}")
+
+    env.close()
+    t.logger.close()
+    return rewards_history
+
+
+def fast_ok(trainer):
+    """The one-launch path applies: a QnetEngine on a HIP device behind a device-mirrored ReplayBuffer whose rows fit
+    the record kernel, and a network the act kernel covers."""
+    from ..buffer.replay_buffer import ReplayBuffer
+    from ..engine import _norm_device
+    eng = getattr(trainer, "_engine", None)
+    rb = trainer.replay_buffer
+    if eng is None or eng.device.type != "cuda" or type(rb) is not ReplayBuffer or _norm_device(rb.device) != eng.device:
+        return False
+    S = int(np.prod(rb.state_shape))
+    if S != eng.cfg.state_dim or S > eng.RECORD_MAX_STATE or S > eng.ACT_MAX_INLINE:
+        return False
+    eng._ensure_bound()
+    return eng.act_ok

@@ -19,12 +19,12 @@ class QRDQNTrainer(DistTrainerBase):
                  epsilon_decay: float = 0.99, update_target_freq: int = 10, device=torch.device("cpu"),
                  network_hidden_sizes: List[int] = [128, 128], num_quantiles: int = 51, kappa: float = 1.0,
                  learning_rate: float = 5e-4, log_dir: str = "logs", batch_size: int = 64, max_batch: int = 4096,
-                 replay_buffer=None):
+                 replay_buffer=None, transition_learning_step: int = 10000):
         self.num_quantiles, self.kappa = num_quantiles, kappa
         q = QRNetwork(state_size, action_size, num_quantiles, network_hidden_sizes)
         t = QRNetwork(state_size, action_size, num_quantiles, network_hidden_sizes)
         self._setup(q, t, state_size, action_size, gamma, epsilon, epsilon_min, epsilon_decay, update_target_freq, device,
-                    learning_rate, log_dir, batch_size, max_batch, replay_buffer)
+                    learning_rate, log_dir, batch_size, max_batch, replay_buffer, transition_learning_step)
         i = torch.arange(0, num_quantiles, device=self.device, dtype=torch.float32)
         self.tau = ((2 * i + 1) / (2 * num_quantiles)).unsqueeze(0)          # (1, N), qr_dqn_trainer.py:89-95
 
@@ -45,3 +45,8 @@ class QRDQNTrainer(DistTrainerBase):
             return int(np.random.randint(self.action_size))
         x = torch.from_numpy(np.asarray(state)).float().unsqueeze(0).to(self.device)
         return self._greedy(self.q_network.get_mean_q_values(x))
+
+    _act_for = select_action
+
+    def _act_epilogue(self):
+        return 2, self.num_quantiles, None

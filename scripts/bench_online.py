@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Environment steps per second of DQNTrainer.train_online: the one-launch path (porl_qnet_act / ReplayBuffer.record /
+in-kernel gather, porl_amd/train/online.py) against the reference loop on the same trainer (select_action + push +
+learn).  Zero-cost environment, S = 8, A = 4, the default [64, 128, 64] QNetwork, batch 64, a 100 k buffer pre-filled
+with 1 000 transitions so that every timed step learns.  Two action regimes, reported separately:
+  greedy  : epsilon = 0 — every step acts through the network
+  explore : epsilon = 1 — every step draws a random action (no forward at all)
+
+    python scripts/bench_online.py [--steps 3000] [--warmup 300]
+
+Prints one JSON line.
+"""
+from __future__ import annotations
+
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from porl_amd.train import online  # noqa: E402
+from porl_amd.train.dqn_trainer import DQNTrainer  # noqa: E402
+
+S, A, B, CAP, PREFILL = 8, 4, 64, 100_000, 1000
+
+
+class ZeroEnv:
+    """No work per step: the same state back, a constant reward, episodes end by truncation only."""
+
+    def __init__(self, max_len):
+        self.max_len = max_len
+        self.s = np.linspace(-1.0, 1.0, S, dtype=np.float32)
+
+    def reset(self, seed=None):
+        self.t = 0
+        return self.s, {}
+
+    def step(self, action):
+        self.t += 1
+        return self.s, 0.5, False, self.t >= self.max_len, {}
+
+    def close(self):
+        pass
+
+
+class NullLogger:
+    def log_step(self, *a):
+        pass
+
+    def log_episode(self, *a):
+        pass
+
+    def close(self):
+        pass
+
+
+def run(fast, eps, steps, warmup):
+    torch.manual_seed(0)
+    np.random.seed(0)
+    t = DQNTrainer(S, A, 0.99, epsilon=eps, epsilon_min=eps, epsilon_decay=1.0, update_target_freq=10, device="cuda",
+                   batch_size=B, transition_learning_step=B)
+    t.logger = NullLogger()
+    rng = np.random.default_rng(1)
+    for _ in range(PREFILL):
+        t.replay_buffer.push(rng.standard_normal(S).astype(np.float32), int(rng.integers(A)), float(rng.standard_normal()),
+                             rng.standard_normal(S).astype(np.float32), False)
+    t.replay_buffer._sync_mirror()
+    orig = online.fast_ok
+    assert orig(t), "the one-launch path does not apply to this trainer"
+    if not fast:
+        online.fast_ok = lambda trainer: False
+    try:
+        with contextlib.redirect_stdout(io.StringIO()):
+            t.train_online(ZeroEnv(warmup), num_episodes=1, max_steps=warmup)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            t.train_online(ZeroEnv(steps), num_episodes=1, max_steps=steps)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+    finally:
+        online.fast_ok = orig
+    return steps / dt
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=3000)
+    ap.add_argument("--warmup", type=int, default=300)
+    a = ap.parse_args()
+    out = {"metric": "train_online env steps/s", "config": dict(S=S, A=A, hidden=[64, 128, 64], batch=B, capacity=CAP,
+                                                                  steps=a.steps, every_step_learns=True)}
+    for name, eps in (("greedy", 0.0), ("explore", 1.0)):
+        fast = run(True, eps, a.steps, a.warmup)
+        plain = run(False, eps, a.steps, a.warmup)
+        out[name] = dict(fast=round(fast, 1), reference_loop=round(plain, 1), ratio=round(fast / plain, 3))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
