@@ -92,6 +92,49 @@ def main():
                            frac_params_beyond_2e6=float(sum(int(((res[True][2][k] - res[False][2][k]).abs() > 2e-6).sum())
                                                             for k in res[True][2]) / sum(v.numel() for v in res[True][2].values())),
                            max_rel_loss_err=float(np.abs(res[True][1][:, :2] / res[False][1][:, :2] - 1).max()))
+    # ---- 3. the same shape update by update from identical state: the error of ONE update, which section 2's trajectory
+    # bound cannot separate from 45 updates of rounding.  Before every update the forced agent gets the plain agent's
+    # parameters, targets, Adam moments and step counters, and both draw the same rows.  From identical moments the new
+    # exp_avg differs by (1 - beta1) * (gradient difference), so |dm| / ((1 - beta1) max|g|) is the gradient error. ------
+    U = 5
+    plain, forced = agent(S, H, B, False), agent(S, H, B, True)
+    rps = {}
+    for a in (plain, forced):
+        a.async_losses = True
+        rps[id(a)] = PackedReplay(replay_rows, S, 2, dev, seed=7)
+
+    def moments(a):
+        out_m = []
+        for opt in (a.v_optimizer, a.goal_policy_optimizer):
+            opt.consolidate_state()
+            st = opt.state_dict()["state"]
+            out_m += [st[i]["exp_avg"].clone() for i in sorted(st)] if st else [None] * len(opt._params)
+        return out_m
+
+    per = []
+    beta1 = plain.v_optimizer.param_groups[0]["betas"][0]
+    for u in range(U):
+        forced.load_state_dict(plain.state_dict())
+        forced.v_optimizer.load_state_dict(plain.v_optimizer.state_dict())
+        forced.goal_policy_optimizer.load_state_dict(plain.goal_policy_optimizer.state_dict())
+        forced.goal_lr_schedule.load_state_dict(plain.goal_lr_schedule.state_dict())
+        m_old = moments(plain)
+        stats = {}
+        for a in (plain, forced):
+            stats[id(a)] = torch.zeros(8, device=dev)
+            a._engine.set_stats(stats[id(a)])
+            a.update_from_replay(rps[id(a)], B)
+        m_p, m_f = moments(plain), moments(forced)
+        grad_err = 0.0
+        for old, mp, mf in zip(m_old, m_p, m_f):
+            g = mp - beta1 * old if old is not None else mp      # (1 - beta1) * g of the plain update
+            grad_err = max(grad_err, float((mf - mp).abs().max()) / max(1e-30, float(g.abs().max())))
+        sd_p, sd_f = plain.state_dict(), forced.state_dict()
+        lp, lf = stats[id(plain)][:2].cpu().numpy(), stats[id(forced)][:2].cpu().numpy()
+        per.append(dict(max_rel_loss_err=float(np.abs(lf / lp - 1).max()), max_rel_grad_err=grad_err,
+                        max_abs_param_err=max(float((sd_f[k] - sd_p[k]).abs().max()) for k in sd_p)))
+    assert forced._exchange.active and getattr(forced, "_exchange_pol", None) is not None and not plain._exchange.active
+    out["headline_per_update"] = per
     torch.cuda.synchronize()
     dist.destroy_process_group()
     print("RCCL_WORLD1 " + json.dumps(out), flush=True)

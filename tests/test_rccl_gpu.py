@@ -46,6 +46,13 @@ def test_world1_nccl_exchange_reproduces_the_plain_update():
     # that many updates fp32 ReLU-mask flips move single weight rows (tests/test_por_gpu.py:_cmp_params_robust) — losses
     # at 1e-5 on every update, all but 5e-3 of the parameters within 2e-6 (measured 1.9e-3), none further than 1e-4
     assert h["max_rel_loss_err"] <= 1e-5 and h["frac_params_beyond_2e6"] <= 5e-3 and h["max_abs_param_err"] <= 1e-4, h
+    # beside that trajectory bound, ONE update at a time from identical state (parameters, targets, Adam moments, step
+    # counters, rows): the split-K order is then the only difference, and it must stay at rounding level — gradients
+    # within 1e-6 of each tensor's largest element, losses within 1e-6 relative, parameters within 2e-6
+    per = out["headline_per_update"]
+    assert len(per) == 5
+    for u in per:
+        assert u["max_rel_grad_err"] <= 1e-6 and u["max_rel_loss_err"] <= 1e-6 and u["max_abs_param_err"] <= 2e-6, per
 
 
 def test_bench_gpus1_through_rccl():
