@@ -11,14 +11,18 @@ EMA + policy step.  Workload at N=1 is BASELINE config 2 (S=60, A=2, H=1024, L=2
 buffer, fp32); at N>1 every rank keeps its own 1.25 M-row shard (N=8 -> the 10 M-row buffer of config 4)
 and draws B=1024 local rows — weak scaling, gradients exchanged with RCCL.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line: nothing else.  At N>1 the line carries
+  dp           : which data-parallel modes ran, which one `value` is from, what failed
+With --full an N=1 run goes on after the timed steps and adds (each --no-* option still drops its part)
+  sustained_1000_updates_per_sec : the same loop again for 5 x 1 000 updates, median
   roofline     : dominant launch (the 4-net hidden-layer fp32-MFMA grouped GEMM) timed with HIP events on its
                  launch stream in a second, instrumented pass
-  cpu_baseline : eager PyTorch-CPU / the numpy oracle (oracle/) timed on the host cores on a bounded sample of the
-                 same workload (rank 0, N=1 only)
-  secondary    : (N=1) BASELINE configs 3 and 5, POR at the class-default width and the headline in the reference's
+  secondary    : BASELINE configs 3 and 5, POR at the class-default width and the headline in the reference's
                  synchronous calling convention — each its own short timed loop, none of them `value`
-  dp           : (N>1) which data-parallel modes ran, which one `value` is from, what failed
+  cpu_baseline : eager PyTorch-CPU / the numpy oracle (oracle/) timed on the host cores on a bounded sample of the
+                 same workload
+and `--workload cql|sorl_enc` adds its instrumented roofline pass and its CPU baseline.
 
 N > 1.  Every GPU process is the CHILD of a supervisor that makes no GPU call: under
 torch.distributed.run each launched rank supervises its own child, for the bare `python bench.py --gpus N` one
@@ -88,7 +92,7 @@ def por_flops_per_sample(h=None):
 
 
 # =====================================================================================================================
-# CPU baselines (rank 0, N=1 only).  oracle/ is test infrastructure: it is imported HERE and nowhere in the timed GPU path.
+# CPU baselines (rank 0, N=1, --full only).  oracle/ is test infrastructure: it is imported HERE and nowhere in the timed GPU path.
 # =====================================================================================================================
 def cpu_baseline(budget_s=12.0):
     """CPU steps/s on the host, same shapes, bounded by wall time: the stronger of (a) eager PyTorch-CPU (MKL,
@@ -161,11 +165,12 @@ def cpu_baseline(budget_s=12.0):
 
 # =====================================================================================================================
 # Secondary workloads: BASELINE configs 3 (CQL) and 5 (SORL + costmap encoder).  `--workload cql|sorl_enc` prints their
-# own line; the default run folds a short form of each into `secondary`.
+# own line; a --full run of the headline folds a short form of each into `secondary`.
 # =====================================================================================================================
-def measure_cql(steps, warmup, with_cpu=True, dump_dir=None):
+def measure_cql(steps, warmup, with_cpu=True, dump_dir=None, with_roofline=True):
     """BASELINE config 3: CQL(H) learn() at B=4096, S=60, A=10, Q-net 64-128-64, 100 k-row buffer resident on the
-    device, rows drawn by the step kernel itself.  dump_dir: the last timed step's losses and networks (dump_outputs)."""
+    device, rows drawn by the step kernel itself.  dump_dir: the last timed step's losses and networks (dump_outputs).
+    with_roofline: the instrumented second pass behind `roofline`."""
     import numpy as np
     import torch
     from porl_amd.train.cql_trainer import CQLTrainer
@@ -199,13 +204,15 @@ def measure_cql(steps, warmup, with_cpu=True, dump_dir=None):
         for prefix, net in (("q_network.", t.q_network), ("target_network.", t.target_network)):
             arrays.update({prefix + k: v for k, v in net.state_dict().items()})
         dump_outputs(dump_dir, arrays)
-    # instrumented second pass: HIP events around the step kernel on its launch stream
-    psteps = max(steps, 50)
-    E.prof_enable(True)
-    for i in range(psteps):
-        t.learn_device_sampled()
-    prof = E.prof_read()
-    E.prof_enable(False)
+    prof = []
+    if with_roofline:
+        # instrumented second pass: HIP events around the step kernel on its launch stream
+        psteps = max(steps, 50)
+        E.prof_enable(True)
+        for i in range(psteps):
+            t.learn_device_sampled()
+        prof = E.prof_read()
+        E.prof_enable(False)
     roof = None
     dom = [p for p in prof if p["name"].startswith(("qnet_fused", "qnet_resident")) and p["launches"]]
     if dom:
@@ -267,11 +274,12 @@ def measure_cql(steps, warmup, with_cpu=True, dump_dir=None):
 
 
 def measure_sorl_enc(steps, warmup, batch=512, angle_bins=360, dist_bins=256, enc_dtype="fp32", with_cpu=True,
-                     dump_dir=None):
+                     dump_dir=None, with_roofline=True):
     """BASELINE config 5: SORL.update with the FasterNet costmap encoder as backbone, S = angle_bins + 2 (beams + goal),
     feature_dim=256, H=512.  One step = encode s, encode s' (train-mode BatchNorm, DropPath), value + policy update.
     fp32 on the reference's 360x256 image is the parity configuration; 84x84 / bf16 are BASELINE's wording.
-    dump_dir: the last timed step's losses and the agent's state (dump_outputs)."""
+    dump_dir: the last timed step's losses and the agent's state (dump_outputs).  with_roofline: the instrumented
+    second pass behind `roofline`."""
     import numpy as np
     import torch
     from types import SimpleNamespace
@@ -323,27 +331,29 @@ def measure_sorl_enc(steps, warmup, batch=512, angle_bins=360, dist_bins=256, en
     if dump_dir:
         # [v_loss, g_loss, min_nll] of the last timed step, then parameters and BatchNorm statistics (encoder included)
         dump_outputs(dump_dir, {"losses": agent._engine.stats[:3], **agent.state_dict()})
-    psteps = min(steps, 10)
-    E.prof_enable(True)
-    for i in range(psteps):
-        one_step(i)
-    prof = E.prof_read()
-    E.prof_enable(False)
-    split = {p["name"]: round(p["total_ms"] / psteps, 4) for p in prof if p["launches"]}
-    gemms = [p for p in prof if p["name"].split(":")[-1].startswith(("gemm_f32_kernel", "gemm_bf16_kernel", "enc_")) and p["launches"]
-             and p["flops"] > 0]
-    dom = max(gemms, key=lambda p: p["total_ms"])
-    ach = dom["flops"] / (dom["total_ms"] * 1e-3) / 1e12
-    hbm = dom["bytes"] / (dom["total_ms"] * 1e-3) / 1e9
     enc_flops = 2 * 2 * Bq * 0.86e9 * (n_ang * n_dist) / (360.0 * 256.0)
-    peak_tf = PEAK_FP32_MFMA_TFLOPS if enc_dtype == "fp32" else PEAK_BF16_MFMA_TFLOPS
-    roof = dict(kernel=dom["name"], launches=dom["launches"], avg_launch_us=1e3 * dom["total_ms"] / dom["launches"], traffic=None,
-                mfma_tflops=ach, mfma_frac=ach / peak_tf, hbm_gbs=hbm, hbm_frac=hbm / PEAK_HBM_GBS,
-                all_kernels_ms_per_step=split)
-    if enc_dtype == "fp32":
-        roof.update(bound="mfma", achieved=ach, peak=peak_tf, unit="TFLOP/s", frac=ach / peak_tf)
-    else:
-        roof.update(bound="hbm", achieved=hbm, peak=PEAK_HBM_GBS, unit="GB/s", frac=hbm / PEAK_HBM_GBS)
+    roof = None
+    if with_roofline:
+        psteps = min(steps, 10)
+        E.prof_enable(True)
+        for i in range(psteps):
+            one_step(i)
+        prof = E.prof_read()
+        E.prof_enable(False)
+        split = {p["name"]: round(p["total_ms"] / psteps, 4) for p in prof if p["launches"]}
+        gemms = [p for p in prof if p["name"].split(":")[-1].startswith(("gemm_f32_kernel", "gemm_bf16_kernel", "enc_")) and p["launches"]
+                 and p["flops"] > 0]
+        dom = max(gemms, key=lambda p: p["total_ms"])
+        ach = dom["flops"] / (dom["total_ms"] * 1e-3) / 1e12
+        hbm = dom["bytes"] / (dom["total_ms"] * 1e-3) / 1e9
+        peak_tf = PEAK_FP32_MFMA_TFLOPS if enc_dtype == "fp32" else PEAK_BF16_MFMA_TFLOPS
+        roof = dict(kernel=dom["name"], launches=dom["launches"], avg_launch_us=1e3 * dom["total_ms"] / dom["launches"], traffic=None,
+                    mfma_tflops=ach, mfma_frac=ach / peak_tf, hbm_gbs=hbm, hbm_frac=hbm / PEAK_HBM_GBS,
+                    all_kernels_ms_per_step=split)
+        if enc_dtype == "fp32":
+            roof.update(bound="mfma", achieved=ach, peak=peak_tf, unit="TFLOP/s", frac=ach / peak_tf)
+        else:
+            roof.update(bound="hbm", achieved=hbm, peak=PEAK_HBM_GBS, unit="GB/s", frac=hbm / PEAK_HBM_GBS)
     out = {"metric": "gradient-steps/sec (SORL update + FasterNet encoder, batch=%d)" % Bq, "value": steps / el,
            "unit": "gradient-steps/sec", "n_gpus": 1, "steps": steps, "warmup": warmup,
            "ms_per_step": 1e3 * el / steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -351,7 +361,9 @@ def measure_sorl_enc(steps, warmup, batch=512, angle_bins=360, dist_bins=256, en
            "data": "synthetic",
            "config": {"workload": f"SORL S={n_ang + 2} F={F} H={Hq} B={Bq} + FasterNet(3,{F}) encoder on {n_ang}x{n_dist} costmaps, "
                                   "2 encoder forwards (train-mode BN, DropPath) + value/policy update per step"},
-           "algorithmic_tflops": enc_flops * steps / el / 1e12, "roofline": roof}
+           "algorithmic_tflops": enc_flops * steps / el / 1e12}
+    if roof:
+        out["roofline"] = roof
     if with_cpu:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import fasternet_oracle as FO
@@ -523,9 +535,14 @@ def main():
     ap.add_argument("--dist-bins", type=int, default=256, help="sorl_enc: costmap columns")
     ap.add_argument("--enc-dtype", default="fp32", choices=["fp32", "bf16", "bf16_operands"],
                     help="sorl_enc: operand type of the encoder's 1x1 / merge convolutions (fp32 = reference parity)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` object (configs 3 / 5, H=256, sync mode)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the sustained rate, the "
+                         "instrumented roofline pass, the `secondary` workloads and the CPU baseline (N=1); the roofline "
+                         "pass and the CPU baseline of --workload cql|sorl_enc")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the POR roofline pass")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="--full without the `secondary` object (configs 3 / 5, H=256, sync mode)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="issue every update back to back on one stream (profiling: kernels never overlap)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -535,11 +552,13 @@ def main():
     if a.steps < 1:
         ap.error("--steps must be at least 1")
     if a.workload == "cql":
-        print(json.dumps(measure_cql(a.steps, a.warmup, not a.no_cpu_baseline, a.dump_outputs)), flush=True)
+        print(json.dumps(measure_cql(a.steps, a.warmup, a.full and not a.no_cpu_baseline, a.dump_outputs,
+                                     with_roofline=a.full)), flush=True)
         return
     if a.workload == "sorl_enc":
         print(json.dumps(measure_sorl_enc(a.steps, a.warmup, a.batch or 512, a.angle_bins, a.dist_bins, a.enc_dtype,
-                                          not a.no_cpu_baseline, a.dump_outputs)), flush=True)
+                                          a.full and not a.no_cpu_baseline, a.dump_outputs, with_roofline=a.full)),
+              flush=True)
         return
     global H, B
     if a.hidden:
@@ -720,7 +739,7 @@ def por_rank(a, force_dp):
             "algorithmic_tflops": steps_per_s * B * world * por_flops_per_sample() / 1e12,
             "final_losses": {"v_loss": float(lh[-1, 0]), "g_loss": float(lh[-1, 1]), "min_nll": float(lh[-1, 2])},
             "update_mode": ("async_losses + two-stream pipelining (opt-in extensions, INTEGRATION.md); the reference's "
-                            "synchronous convention is secondary.por_sync_mode") if mode == "pipelined" else mode,
+                            "synchronous convention is secondary.por_sync_mode of a --full run") if mode == "pipelined" else mode,
             "setup_spinup_ms": spin_ms,
             "rccl_ranks": dist.get_world_size() if dp else 1,
             "backend": (dist.get_backend() if dp else "none"),
@@ -770,11 +789,12 @@ def por_rank(a, force_dp):
         # networks it left (value twins, their target, goal policy)
         dump_outputs(a.dump_outputs, {"losses": res["lh"][-1], **agent.state_dict()})
 
+    # From here on --full only: the headline needs none of it.
     # Not `value`: the same loop again for 1 000 updates, five times, median.  The first ~20 updates after a device sync
     # run ~4 % slower than the steady state (scripts/bench_ramp.py: 315 against 303 us each) and a K = 20 run also pays the
     # pipeline's fill and drain (~0.3 ms) once; a training job runs millions of updates, so the sustained rate is reported
     # beside the contract's K-step figure.
-    if a.steps < 1000 and os.environ.get("PORL_BENCH_SUSTAINED", "1") != "0":
+    if a.full and a.steps < 1000 and os.environ.get("PORL_BENCH_SUSTAINED", "1") != "0":
         n_s, rates = 1000, []
         for _ in range(5):
             barrier()
@@ -787,11 +807,11 @@ def por_rank(a, force_dp):
         out["sustained_1000_updates_per_sec"] = float(np.median(rates))
         out["sustained_runs"] = [round(r, 1) for r in rates]
 
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         out["roofline"] = por_roofline(E, agent, one_step, a, mode)
     del agent, one_step, res
 
-    if not a.no_secondary and H == 1024 and B == 1024:
+    if a.full and not a.no_secondary and H == 1024 and B == 1024:
         sec = {}
         t_sec = time.perf_counter()
 
@@ -833,7 +853,7 @@ def por_rank(a, force_dp):
         guarded("sorl_enc_bf16_360x256_b512", lambda: _brief(measure_sorl_enc(max(10, min(a.steps, 20)), 3, 512, 360, 256, "bf16", False)))
         out["secondary"] = sec
 
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
         out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
     print(json.dumps(out), flush=True)

@@ -9,8 +9,8 @@ RD=${PORL_ROUND:-r03}
 O=$R/gpurun_out/$RD/prof2
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-C="python3 $R/bench.py --workload cql --steps 40 --warmup 5 --no-cpu-baseline"
-S="python3 $R/bench.py --workload sorl_enc --batch 256 --steps 2 --warmup 1 --no-cpu-baseline"
+C="python3 $R/bench.py --workload cql --steps 40 --warmup 5 --full --no-cpu-baseline"
+S="python3 $R/bench.py --workload sorl_enc --batch 256 --steps 2 --warmup 1 --full --no-cpu-baseline"
 rocprofv3 --pmc FETCH_SIZE -d $O/cql_fetch -o t -- $C > /dev/null 2> $O/cql_fetch.err
 rocprofv3 --pmc WRITE_SIZE -d $O/cql_write -o t -- $C > /dev/null 2> $O/cql_write.err
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAVE_CYCLES -d $O/cql_mfma -o t -- $C > /dev/null 2> $O/cql_mfma.err
