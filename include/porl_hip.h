@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define PORL_ABI_VERSION 7
+#define PORL_ABI_VERSION 8
 #define PORL_MAX_HIDDEN 8
 
 #define PORL_OK 0
@@ -165,6 +165,21 @@ int porl_iql_policy_backward(porl_iql* h, const porl_iql_hyper* hp, void* stream
 int porl_iql_policy_apply(porl_iql* h, const porl_iql_hyper* hp, void* stream);
 /* The four phases back to back (single-GPU update; batch must have been loaded). */
 int porl_iql_step(porl_iql* h, const porl_iql_hyper* hp, void* stream);
+/* Policy-only step: the policy phase of two-phase SORL training with FROZEN value nets — reference agent/sorl.py:154-176
+ * (SORL.policy_update) with the TD target of sorl.py:85-89, which that method uses without assigning it.  For the loaded
+ * batch: the target twin on s' and the online twin on s run forward-only beside the policy MLP (five nets per layer in
+ * one launch, no V-net activation kept), one head kernel turns their scalar outputs into
+ *     target_v = r + (1 - d) * discount * min(target),  adv = target_v - min(online),
+ *     weight   = min(exp(alpha * adv), 100)   (cfg.weight_mode 1)   or   min(exp(adv / alpha), 100)   (weight_mode 0),
+ * then the weighted NLL, its backward and Adam on the policy as in the joint update (hp->policy_lr, hp->policy_step).
+ * Writes grads_pol, params_pol, adam_*_pol, stats[1] = g_loss share, stats[2] = min NLL; params_vf, params_tgt,
+ * grads_vf, adam_*_vf and stats[0] are not written.  Errors as porl_iql_step (unbound engine, no batch loaded, no
+ * policy target in the batch: an error code, nothing launched).
+ *   porl_iql_policy_only_step    : the whole step in one call, combines folded into the Adam launch.
+ *   porl_iql_policy_only_forward : its forward half; porl_iql_policy_backward and porl_iql_policy_apply on the same
+ *       batch complete it (a data-parallel caller all-reduces grads_pol between those two). */
+int porl_iql_policy_only_forward(porl_iql* h, const porl_iql_hyper* hp, void* stream);
+int porl_iql_policy_only_step(porl_iql* h, const porl_iql_hyper* hp, void* stream);
 
 /* Forward-only paths: TwinV.both (value_functions.py:38-39) on vf (which=0) or the target (which=1),
  * and the policy mean (policy.py:19 / sorl.py:71-76).  x is (batch, obs_dim) with row stride x_rs. */

@@ -410,12 +410,22 @@ class IqlAgentBase(nn.Module):
         self.flush()
         return super().load_state_dict(*args, **kwargs)
 
-    def _value_update(self, obs, next_obs, rew, term, v_opt):
+    def _load(self, obs, next_obs, rew, term, pol_target, replay, batch):
+        """Stage the minibatch: the given tensors, or `batch` rows drawn on the device from `replay` (PackedReplay)."""
+        eng = self._engine
+        if replay is None:
+            return eng.load_batch(obs, next_obs, rew, term, pol_target)
+        B = eng.load_batch_sampled(replay.rows, batch, replay.seed, replay.draws, replay.act_dim,
+                                   eng.cfg.weight_mode == 1)
+        replay.draws += 1
+        return B
+
+    def _value_update(self, obs, next_obs, rew, term, v_opt, replay=None, batch=None):
         eng, ex = self._engine, self._exchange
         eng.join()
         eng._ensure_bound()
         eng.set_mode(IqlEngine.MODE_FOLD_COMBINE if not ex.active else 0)
-        B = eng.load_batch(obs, next_obs, rew, term, None)
+        B = self._load(obs, next_obs, rew, term, None, replay, batch)
         v_opt.step_count += 1
         hp = self._hyper(B, v_opt, v_opt)
         eng.value_backward(hp)
@@ -430,6 +440,52 @@ class IqlAgentBase(nn.Module):
             ex.allreduce_sum_(eng.grads_vf)
             ex.allreduce_stats_(eng.stats)
         eng.value_apply(hp)
+
+    def _policy_update(self, obs, next_obs, rew, term, pol_target, p_opt, sched, replay=None, batch=None):
+        """Policy step with the value nets frozen (reference sorl.py:154-176; sibling of `_value_update`): TD target from
+        the target twin, advantage from the online twin, weighted NLL, backward, Adam on the policy group only.  The
+        value optimizer's step count and moments, the value nets and the target nets do not move; stats[0] keeps the
+        last v_loss.  A rejected call (e.g. batch > max_batch) launches nothing and leaves every counter as it was."""
+        eng, ex = self._engine, self._exchange
+        eng.join()                             # a pipelined update may still have its policy phase on the side stream
+        eng._ensure_bound()
+        eng.set_mode(IqlEngine.MODE_FOLD_COMBINE if not ex.active else 0)
+        B = self._load(obs, next_obs, rew, term, pol_target, replay, batch)
+        p_opt.step_count += 1
+        hp = self._hyper(B, p_opt, p_opt)      # (value_lr / value_step are not read by the policy-only step)
+        try:
+            if not ex.active:
+                eng.policy_only(hp)
+            else:
+                eng.policy_only_forward(hp)
+                eng.policy_backward(hp)
+        except Exception:
+            p_opt.step_count -= 1
+            raise
+        if ex.active:
+            if self._sharded():
+                self._sharded_apply(IqlEngine.GROUP_POL, hp, p_opt)
+            else:
+                p_opt._unshard()
+                ex.allreduce_sum_(eng.grads_pol)
+                eng.policy_apply(hp)
+            if not self.async_losses:          # async mode: statistics stay per-rank shares, as in _full_update
+                ex.allreduce_stats_(eng.stats, first=1)
+        sched.step()
+
+    def _policy_loss(self):
+        """g_loss of the last policy-only step: a float, or the stats[1:2] device view under async_losses."""
+        if self.async_losses:
+            return self._engine.stats[1:2]
+        g_loss, min_nlp = self._engine.stats[1:3].tolist()            # the one host sync of the step
+        if math.isnan(g_loss):
+            raise ValueError("NaN loss: non-finite values in the minibatch or the parameters")
+        if min_nlp <= 0 and not IqlAgentBase._warned_nll:
+            IqlAgentBase._warned_nll = True
+            warnings.warn("per-sample NLL <= 0 in this batch (the reference drops into pdb here, "
+                          "agent/por.py:104-105); continuing", RuntimeWarning)
+        self.last_min_nll = min_nlp
+        return g_loss
 
     def _losses(self):
         if self.async_losses:

@@ -2,11 +2,17 @@
 encoder as `backbone` (sorl_train.py:29-33: `FasterNet(3, args.feature_dim)`, porl_amd/agent/fasternet.py).
 
 Same constructor and attribute names (`v_net`, `policy`, `v_tgt`, `v_optimizer`, `policy_optimizer`,
-`lr_schedule`), `update`, `vf_update`, `select_action`.  Value step == POR's; the policy step is
+`lr_schedule`), `update`, `vf_update`, `policy_update`, `select_action`.  Value step == POR's; the policy step is
 advantage-weighted behaviour cloning of the dataset actions with a tanh-bounded mean and
 weight = min(exp(alpha * adv), 100) — alpha MULTIPLIES here (sorl.py:104), unlike POR.
 
-`policy_update` is broken upstream (NameError on `target_v`, sorl.py:163) and is not provided.
+`policy_update` (sorl.py:154-176), the policy phase of the two-phase script sorl_train_v0.py:57-103, is broken upstream:
+it reads `target_v` (sorl.py:163) without assigning it.  Here it behaves as evidently intended: the two missing lines are
+taken from `update` / `vf_update` of the same file (sorl.py:85-89), `next_v = v_tgt(s')` without gradient and
+`target_v = r + (1 - d) * discount * next_v`; everything else is the method as written.  It runs as a step of its own
+on the device (five forward-only nets per layer in one launch, one head kernel for target, advantage and weight, the
+policy's backward and Adam) and leaves the value nets, the target nets and the value optimizer untouched.
+`vf_update_from_replay` / `policy_update_from_replay` are the two phases on rows drawn on the device.
 """
 from __future__ import annotations
 
@@ -76,6 +82,29 @@ class SORL(IqlAgentBase):
         if agent.async_losses:
             return agent._engine.stats[:1]
         return float(agent._engine.stats[0])
+
+    def policy_update(agent, observations, actions, rewards, next_observations, terminals):
+        """Policy step only, value nets frozen (reference sorl.py:154-176, with the TD target of sorl.py:85-89 that the
+        reference method reads but never assigns) -> g_loss."""
+        if agent.backbone is not None:
+            observations = agent.backbone(observations)
+            next_observations = agent.backbone(next_observations)
+        agent._policy_update(observations, next_observations, rewards, terminals, actions,
+                             agent.policy_optimizer, agent.lr_schedule)
+        return agent._policy_loss()
+
+    def vf_update_from_replay(agent, replay, batch_size):
+        """Extension (not in the reference): `vf_update` on rows drawn on the device from a PackedReplay."""
+        agent._value_update(None, None, None, None, agent.v_optimizer, replay=replay, batch=batch_size)
+        if agent.async_losses:
+            return agent._engine.stats[:1]
+        return float(agent._engine.stats[0])
+
+    def policy_update_from_replay(agent, replay, batch_size):
+        """Extension (not in the reference): `policy_update` on rows drawn on the device from a PackedReplay."""
+        agent._policy_update(None, None, None, None, None, agent.policy_optimizer, agent.lr_schedule,
+                             replay=replay, batch=batch_size)
+        return agent._policy_loss()
 
     def update_from_replay(agent, replay, batch_size):
         """Extension (not in the reference): `update` on rows drawn on the device from a PackedReplay."""

@@ -97,12 +97,53 @@ __global__ __launch_bounds__(1024) void value_loss_kernel(const ValueLossArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Policy-only step (SORL.policy_update, agent/sorl.py:154-176 with the TD target of sorl.py:85-89): the scalar heads of
+// the four forward-only V nets in one launch.  v = sum(parts) + b for {target1, target2} on s' and {online1, online2}
+// on s (headparts layout as above: [part][B] per net), then
+//   target_v = r + (1 - d) * discount * min(target),  adv = target_v - min(online),
+//   weight   = min(exp(alpha * adv), 100)  (weight_mode 1)  or  min(exp(adv / alpha), 100)  (weight_mode 0).
+// One wave per row: lane p takes parts p, p + 64, ... of all four nets (every load of the row in flight together), a
+// butterfly sum per net — the same partials in the same order as relu_head_bwd_kernel / policy_nll_kernel add them.
+// policy_nll_kernel then reads `weight` instead of building it from the value phase's target_v.
+// grid ceil(B / PW_ROWS_PER_BLOCK), block 256.
+// ---------------------------------------------------------------------------------------------------
+struct PolicyWeightArgs {
+  const float* hp_t[2]; const float* hp_v[2];   // head partial sums, [parts][B] each
+  const float* b_t[2]; const float* b_v[2];     // scalar output biases (device pointers)
+  const float* rew; const float* term;
+  float* target_v; float* weight;               // (B) each
+  int B, parts, weight_mode;
+  float discount, alpha;
+};
+constexpr int PW_ROWS_PER_BLOCK = 4;     // one row per wave
+
+__global__ __launch_bounds__(256) void policy_weight_kernel(const PolicyWeightArgs a) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x * PW_ROWS_PER_BLOCK + wave;
+  if (b >= a.B) return;                  // whole waves leave; no block-level barrier below
+  float t0 = 0.f, t1 = 0.f, v0 = 0.f, v1 = 0.f;
+  for (int p = lane; p < a.parts; p += 64) {
+    const size_t o = (size_t)p * a.B + b;
+    t0 += a.hp_t[0][o]; t1 += a.hp_t[1][o]; v0 += a.hp_v[0][o]; v1 += a.hp_v[1][o];
+  }
+  const float r = a.rew[b], d = a.term[b];
+  t0 = wave_sum(t0); t1 = wave_sum(t1); v0 = wave_sum(v0); v1 = wave_sum(v1);
+  if (lane != 0) return;
+  const float next_v = fminf(t0 + a.b_t[0][0], t1 + a.b_t[1][0]);
+  const float tgt = r + (1.f - d) * a.discount * next_v;
+  const float adv = tgt - fminf(v0 + a.b_v[0][0], v1 + a.b_v[1][0]);
+  a.target_v[b] = tgt;
+  a.weight[b] = fminf(expf(a.weight_mode ? a.alpha * adv : adv / a.alpha), EXP_ADV_MAX);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // advantage weight + diagonal-Gaussian NLL + its gradient   (agent/por.py:97-106, policy.py:18-23)
 //   one wave per row, lane j handles columns j, j+64, ...
 // ---------------------------------------------------------------------------------------------------
 struct PolicyNllArgs {
   const float* hp_v[2]; const float* b_v[2]; int parts;   // updated twin V heads
   const float* target_v;
+  const float* weight;                                     // non-null (policy-only step): the finished per-row weights of policy_weight_kernel; target_v and the head partials are then not read (parts = 0)
   const float* mean_slab; int nslab; long slab_stride;     // pre-bias mean = sum of split-K slabs
   const float* mean_bias; const float* log_std;
   const float* x; int ldx;                                 // regression target (s' or actions)
@@ -151,7 +192,7 @@ __global__ __launch_bounds__(256) void policy_nll_kernel(const PolicyNllArgs a) 
   for (int b = row0 + wave; fast && b < row1; b += 4) {
     const bool pv = lane < a.parts, cv = lane < a.D;
     const float h0 = a.hp_v[0][pv ? (size_t)lane * a.B + b : 0], h1 = a.hp_v[1][pv ? (size_t)lane * a.B + b : 0];
-    const float tv = a.target_v[b];
+    const float tv = a.weight ? a.weight[b] : a.target_v[b];
     float ms[NLL_FAST_SLABS];
 #pragma unroll
     for (int s = 0; s < NLL_FAST_SLABS; ++s) {
@@ -162,7 +203,7 @@ __global__ __launch_bounds__(256) void policy_nll_kernel(const PolicyNllArgs a) 
     const float xv = a.x[cv ? (size_t)b * a.ldx + lane : 0];
     const float v0 = wave_sum(pv ? h0 : 0.f), v1 = wave_sum(pv ? h1 : 0.f);
     const float adv = tv - fminf(v0 + bv0, v1 + bv1);
-    const float wgt = fminf(expf(a.weight_mode ? a.alpha * adv : adv / a.alpha), EXP_ADV_MAX);
+    const float wgt = a.weight ? tv : fminf(expf(a.weight_mode ? a.alpha * adv : adv / a.alpha), EXP_ADV_MAX);
     const float wb = wgt * a.inv_batch;
     float m = ms[0];
 #pragma unroll
@@ -190,8 +231,8 @@ __global__ __launch_bounds__(256) void policy_nll_kernel(const PolicyNllArgs a) 
       v1 += a.hp_v[1][(size_t)p * a.B + b];
     }
     v0 = wave_sum(v0); v1 = wave_sum(v1);
-    const float adv = a.target_v[b] - fminf(v0 + bv0, v1 + bv1);
-    const float wgt = fminf(expf(a.weight_mode ? a.alpha * adv : adv / a.alpha), EXP_ADV_MAX);
+    const float adv = a.weight ? 0.f : a.target_v[b] - fminf(v0 + bv0, v1 + bv1);
+    const float wgt = a.weight ? a.weight[b] : fminf(expf(a.weight_mode ? a.alpha * adv : adv / a.alpha), EXP_ADV_MAX);
     const float wb = wgt * a.inv_batch;
     float zz = 0.f;
     float z[NLL_MAX_COLS_PER_LANE], mu[NLL_MAX_COLS_PER_LANE];

@@ -259,6 +259,7 @@ struct Workspace {
   int64_t xhat_v[2][PORL_MAX_HIDDEN], rstd_v[2][PORL_MAX_HIDDEN];   // LayerNorm only
   int64_t ln_dg[2], ln_db[2], ln_dh[2];
   int64_t head_part[2], head_loss, head_db[2];                       // relu_head_bwd partials
+  int64_t pol_w;                                                     // policy-only step: per-row weights (policy_weight_kernel)
   int64_t total;
 };
 
@@ -417,7 +418,8 @@ int iql_launch(const porl_iql* h, GemmGroup& g, int tile, bool policy, hipStream
   return launch_group(g, tile, t, s, !short_blocks(h) ? -1 : policy ? t.iql_pad_policy : t.iql_pad_value);
 }
 
-// One hidden layer of up to 4 MLPs as one grouped launch (+ one LayerNorm launch for the nets that have it).
+// One hidden layer of up to MAX_FWD_NETS MLPs (at most 4 of them with LayerNorm) as one grouped launch (+ one LayerNorm launch for the nets that have it).
+constexpr int MAX_FWD_NETS = 5;      // the policy-only step: target twin, online twin, policy
 struct FwdNet {
   const float* in; int ldin;       // (B, K)
   const float* W; const float* b;  // (H, K), (H)
@@ -546,6 +548,7 @@ int porl_iql_create(const porl_iql_cfg* c, porl_iql** out) {
       w.ln_dg[i] = take((int64_t)nln * H); w.ln_db[i] = take((int64_t)nln * H); w.ln_dh[i] = take((int64_t)nln * H);
     }
   }
+  w.pol_w = take(B);
   w.total = o;
   *out = h;
   return PORL_OK;
@@ -1059,7 +1062,11 @@ int porl_iql_policy_prefetch(porl_iql* h, void* stream) {
 // part: 1 = forward half only (second twin forward, policy forward, mean, weights + NLL + dL/dmean: everything of the
 // policy phase that reads the VALUE parameters), 2 = gradient half only (needs the forward half of the same batch),
 // 3 = both.
-static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream_t s, ReduceArgs* defer, int part = 3) {
+// only_policy: the policy-only step (porl_iql_policy_only_*).  Its forward half runs all five nets forward-only — target
+// twin on s', online twin on s, policy on s — in one grouped launch per layer, keeps no V-net activation, and takes the
+// per-row weights from policy_weight_kernel (TD target included) instead of the value phase's target_v.
+static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream_t s, ReduceArgs* defer, int part = 3,
+                                bool only_policy = false) {
   if (!h->have_pol_target) PORL_FAIL(PORL_ERR_INVALID, "policy step needs pol_target in porl_iql_load_batch");
   const int B = h->batch, S = h->cfg.obs_dim, H = h->cfg.hidden_dim, L = h->cfg.n_hidden, D = h->cfg.pol_out_dim;
   const int Hp = h->Hp, Dp = h->Dp;
@@ -1077,8 +1084,54 @@ static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream
   // -- forward: updated twins (head only) + policy hidden layers, 3 nets per launch; the policy net is left out
   //    when porl_iql_policy_prefetch already ran it for this batch ---------------------------------------------
   const bool pre = h->pol_prefetched;
+  const bool pre_weight = only_policy;
   h->pol_prefetched = false;
-  for (int l = 0; l < L; ++l) {
+  if (only_policy) {
+    const float* Pt = h->buf.params_tgt;
+    for (int l = 0; l < L; ++l) {
+      FwdNet nets[MAX_FWD_NETS];
+      const int K = l == 0 ? S : H;
+      const bool last = l == L - 1;
+      for (int n = 0; n < 4; ++n) {
+        const bool tgt = n < 2;
+        const int i = n & 1;
+        const float* P = tgt ? Pt : Pv;
+        const int64_t* act = tgt ? ws.act_t[i] : ws.act_q[i];      // two ping-pong scratch buffers per net
+        FwdNet& f = nets[n];
+        if (l == 0) { f.in = W + (tgt ? ws.xn : ws.xs_slot[h->slot]); f.ldin = h->Sp; }
+        else { f.in = W + act[(l - 1) & 1]; f.ldin = Hp; }
+        f.W = P + h->v[i].w[l]; f.b = P + h->v[i].b[l];
+        f.out = (last && !LN) ? nullptr : W + act[l & 1];
+        f.headw = P + h->v[i].w[L]; f.headout = W + (tgt ? ws.hp_t[i] : ws.hp_q[i]);
+        if (LN) { f.ln_g = P + h->v[i].lnw[l]; f.ln_b = P + h->v[i].lnb[l]; }
+      }
+      int first = 4;
+      if (!pre) {
+        FwdNet& f = nets[4];
+        if (l == 0) { f.in = W + ws.xs_slot[h->slot]; f.ldin = h->Sp; }
+        else { f.in = W + ws.act_p[l - 1]; f.ldin = Hp; }
+        f.W = Pp + h->pol.w[l]; f.b = Pp + h->pol.b[l];
+        f.out = W + ws.act_p[l]; f.headw = nullptr; f.headout = nullptr;
+        first = 5;
+      }
+      g_phase = l == 0 ? "O1.L0fwd:" : "O2.fwd:";
+      PORL_TRY(fwd_hidden_layer(h, nets, first, B, K, last, &parts, true, s));
+    }
+    g_phase = "O3.head:";
+    PolicyWeightArgs a{};
+    for (int i = 0; i < 2; ++i) {
+      a.hp_t[i] = W + ws.hp_t[i]; a.hp_v[i] = W + ws.hp_q[i];
+      a.b_t[i] = Pt + h->v[i].b[L]; a.b_v[i] = Pv + h->v[i].b[L];
+    }
+    a.rew = W + ws.rew; a.term = W + ws.term; a.target_v = W + ws.target_v_slot[h->slot]; a.weight = W + ws.pol_w;
+    a.B = B; a.parts = parts; a.weight_mode = h->cfg.weight_mode; a.discount = hp->discount; a.alpha = hp->alpha;
+    {
+      ProfScope ps("policy_weight_kernel", s, 0.0, 4.0 * B * (4.0 * parts + 4.0));
+      hipLaunchKernelGGL(policy_weight_kernel, dim3(cdiv(B, PW_ROWS_PER_BLOCK)), dim3(256), 0, s, a);
+    }
+    PORL_HIP(hipGetLastError());
+  }
+  for (int l = 0; l < L && !only_policy; ++l) {
     FwdNet nets[3];
     const int K = l == 0 ? S : H;
     const bool last = l == L - 1;
@@ -1100,15 +1153,16 @@ static int policy_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream
     PORL_TRY(fwd_hidden_layer(h, nets, pre ? 2 : 3, B, K, last, &parts, true, s));
   }
   int nslab = h->pol_nslab;
-  g_phase = "P3.mean:";
+  g_phase = only_policy ? "O4.mean:" : "P3.mean:";
   if (!pre) PORL_TRY(policy_mean_slabs(h, B, &nslab, true, s));
-  g_phase = "P4.";
+  g_phase = only_policy ? "O5." : "P4.";
 
   // -- advantage weights, NLL, dL/dmean, dL/dlog_std --------------------------------------------------
   {
     PolicyNllArgs a{};
     for (int i = 0; i < 2; ++i) { a.hp_v[i] = W + ws.hp_q[i]; a.b_v[i] = Pv + h->v[i].b[L]; }
-    a.parts = parts; a.target_v = W + ws.target_v_slot[h->slot];
+    a.parts = pre_weight ? 0 : parts; a.target_v = W + ws.target_v_slot[h->slot];
+    a.weight = pre_weight ? W + ws.pol_w : nullptr;
     a.mean_slab = W + ws.slab_mean; a.nslab = nslab; a.slab_stride = (long)B * Dp;
     a.mean_bias = Pp + h->pol.b[L]; a.log_std = Pp + h->logstd_off;
     a.x = W + ws.xt_slot[h->slot]; a.ldx = Dp; a.dmean = W + ws.dmu; a.ldd = Dp;
@@ -1250,6 +1304,35 @@ int porl_iql_step(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
   fin = ReduceArgs{};
   PORL_TRY(policy_backward_impl(h, hp, s, h->tune.iql_fold ? &fin : nullptr));
   g_phase = "P9.";
+  PORL_TRY(adam_launch(h->buf.params_pol, h->buf.grads_pol, h->buf.adam_m_pol, h->buf.adam_v_pol, nullptr, h->n_pol,
+                       hp->policy_lr, hp->policy_step, hp->adam_beta1, hp->adam_beta2, hp->adam_eps, 0.0, s, &fin));
+  g_phase = "";
+  return PORL_OK;
+}
+
+// Policy-only step (SORL.policy_update, reference agent/sorl.py:154-176 + the TD target of sorl.py:85-89): the value
+// nets are read, never written.  Forward half = five forward-only nets per layer in one launch, policy_weight_kernel,
+// mean, NLL; then the gradient half and Adam of the ordinary policy phase.  2 L + 5 launches at n_hidden = L (9 at L = 2;
+// the joint update takes 14, each plus the minibatch load).
+int porl_iql_policy_only_forward(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
+  PORL_TRY(check_ready(h, true)); DevGuard _dg(h->device);
+  if (!hp) PORL_FAIL(PORL_ERR_INVALID, "null hyper-parameters");
+  h->pol_fwd_done = false;             // a forward half of the joint update's policy phase does not stand in for this one
+  return policy_backward_impl(h, hp, (hipStream_t)stream, nullptr, 1, true);
+}
+
+// porl_iql_policy_only_forward + porl_iql_policy_backward + porl_iql_policy_apply in one call, the combine folded into
+// the Adam launch (single-GPU update; batch must have been loaded).  stats[1] = g_loss, stats[2] = min NLL; stats[0],
+// grads_vf, adam_*_vf, params_vf and params_tgt are not written.
+int porl_iql_policy_only_step(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
+  PORL_TRY(check_ready(h, true)); DevGuard _dg(h->device);
+  if (!hp) PORL_FAIL(PORL_ERR_INVALID, "null hyper-parameters");
+  if (!h->have_pol_target) PORL_FAIL(PORL_ERR_INVALID, "policy step needs pol_target in porl_iql_load_batch");
+  hipStream_t s = (hipStream_t)stream;
+  h->pol_fwd_done = false;
+  ReduceArgs fin{};
+  PORL_TRY(policy_backward_impl(h, hp, s, h->tune.iql_fold ? &fin : nullptr, 3, true));
+  g_phase = "O9.";
   PORL_TRY(adam_launch(h->buf.params_pol, h->buf.grads_pol, h->buf.adam_m_pol, h->buf.adam_v_pol, nullptr, h->n_pol,
                        hp->policy_lr, hp->policy_step, hp->adam_beta1, hp->adam_beta2, hp->adam_eps, 0.0, s, &fin));
   g_phase = "";

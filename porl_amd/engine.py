@@ -274,6 +274,9 @@ class IqlEngine:
     def policy_backward(self, hp): self._phase("porl_iql_policy_backward", hp)
     def policy_apply(self, hp): self._phase("porl_iql_policy_apply", hp)
     def step(self, hp): self._phase("porl_iql_step", hp)
+    # policy-only step (frozen value nets): the whole step, or its forward half followed by policy_backward / policy_apply
+    def policy_only(self, hp): self._phase("porl_iql_policy_only_step", hp)
+    def policy_only_forward(self, hp): self._phase("porl_iql_policy_only_forward", hp)
 
     def update_pipelined(self, hp, replay, batch, seq, wait_policy_seq, wait_fwd_seq, write_policy):
         """One pipelined update on rows drawn from `replay` (PackedReplay): value phase on the current stream, policy

@@ -82,11 +82,12 @@ class GradExchange:
         d.all_gather_into_tensor(flat, self.slice_of(flat), group=self.group)
         return flat
 
-    def allreduce_stats_(self, stats: torch.Tensor):
-        """stats[0:2] = (v_loss, g_loss) shares -> SUM; stats[2] = min NLL -> MIN."""
+    def allreduce_stats_(self, stats: torch.Tensor, first=0):
+        """stats[0:2] = (v_loss, g_loss) shares -> SUM; stats[2] = min NLL -> MIN.  `first=1` (policy-only step) leaves
+        stats[0], the last value step's already reduced v_loss, alone."""
         if self.active:
             d = _dist()
-            d.all_reduce(stats[0:2], op=d.ReduceOp.SUM, group=self.group)
+            d.all_reduce(stats[first:2], op=d.ReduceOp.SUM, group=self.group)
             d.all_reduce(stats[2:3], op=d.ReduceOp.MIN, group=self.group)
         return stats
 
