@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define PORL_ABI_VERSION 8
+#define PORL_ABI_VERSION 9
 #define PORL_MAX_HIDDEN 8
 
 #define PORL_OK 0
@@ -493,6 +493,18 @@ int porl_enc_tensor_info(const porl_enc* h, int32_t index, int64_t* offset, int6
 int porl_enc_norm_info(const porl_enc* h, int32_t index, int64_t* mean_offset, int64_t* var_offset,
                        int32_t* channels, char* name, int32_t name_len);
 int porl_enc_bind(porl_enc* h, float* params, float* bn_stats, float* workspace);
+/* Where the last porl_enc_forward left its intermediate results in the workspace (a pure host query; the contents are
+ * valid until the next forward).  Tap `which` of a batch of b samples is a dense row-major (b * rows_per_sample, cols)
+ * matrix, NHWC position rows, starting offset_floats FLOATS into the workspace whatever its element type.  elem_bytes is
+ * 2 (bf16) for the two stage outputs exactly when the forward runs the bf16-activation branch (bf16_operands == 2 on
+ * the architecture it is instantiated for), 4 (fp32) otherwise.  All four output pointers are required. */
+#define PORL_ENC_TAP_STAGE1 0   /* output of the last stage-1 MLPBlock, rows_per_sample = (n_ang/4) * (n_dist/4), cols = E */
+#define PORL_ENC_TAP_STAGE2 1   /* output of the last stage-2 MLPBlock, (n_ang/8) * (n_dist/8) rows of 2E */
+#define PORL_ENC_TAP_POOLED 2   /* global average pool, one row of 2E per sample, fp32 */
+#define PORL_ENC_TAP_PREHEAD 3  /* relu(1x1 conv) before the Linear head, one row of feature_dim per sample, fp32 */
+#define PORL_ENC_TAPS 4
+int porl_enc_tap_info(const porl_enc* h, int32_t which, int64_t* offset_floats, int64_t* rows_per_sample,
+                      int32_t* cols, int32_t* elem_bytes);
 /* The encoder keeps permuted copies of its convolution weights in the workspace and refreshes them on the first
  * forward after porl_enc_bind.  Call this after writing new values into `params` (load_state_dict, an optimizer step on
  * the backbone) so the next forward refreshes them again. */

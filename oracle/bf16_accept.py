@@ -1,0 +1,108 @@
+"""Acceptance rule of the bf16 encoder tests — TEST INFRASTRUCTURE ONLY (tests/test_bf16_oracle.py checks the rule
+itself on the CPU, tests/test_encoder_bf16_gpu.py applies it to the kernels).
+
+Three results of the same forward meet here:
+  got    what is under test (the HIP kernels),
+  ref    oracle.fasternet_oracle.forward_faithful with fp64 products,
+  ref32  the same oracle with fp32 products: a second CORRECT realisation of the same rounding scheme.
+d_ref = distance(ref32, ref) is how far two correct implementations sit from each other (an fp32-vs-fp64 difference
+in an accumulator now and then lands on the other side of a bf16 rounding boundary, and the flip travels on).  The
+kernels' MFMA accumulation order is a third realisation of that error class, so `got` may be up to FACTOR x d_ref
+from `ref`, with floors where d_ref is (nearly) zero, and under caps that hold whatever d_ref says.  If FACTOR x d_ref
+itself exceeds a cap the comparison proves nothing and is reported as VACUOUS, which is a failure, not a pass.
+
+Metric of a bf16 tensor: steps = |got - ref| / (2^-8 max(|ref|, rms(ref))) — the rounding error of one bf16
+conversion of `ref` is at most 1 step; elements near zero are measured on the tensor's scale, so a sign change there
+is not inflated.  (Two neighbouring bf16 values are up to 2 steps apart just above a power of two: a single flipped
+rounding can therefore read up to 2; d_ref sees such flips as well and the bound follows it.)
+Metric of an fp32 quantity: |got - ref| / rms(ref), or / `scale` where the caller names one (running_mean).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+FACTOR = 4.0
+FLOOR_MAX_STEPS = 1.01          # one conversion's worth, whatever d_ref
+FLOOR_SHARE = 1e-4              # share of elements beyond one step
+# Mean of the steps.  It needs a floor too (without one a second correct fp32 realisation already fails against the
+# first: 1.8e-5 vs 4 x 2.5e-6 at stage 1 of the 84 x 84 case, tests/test_bf16_oracle.py), and the two floors above say
+# nothing about it — elements at or below one step count in neither.  What sets it is the workload: ~90 % of the patches
+# of a costmap are empty, so most rows of a stage are IDENTICAL per sample class, and one legitimately flipped rounding of
+# that background value shows in one channel at every such row (the oracle pair shows it on the CPU: 264 rows of channel
+# 74 at once, 84 x 84 eval).  One such event is at most 2 steps (the step metric, see above) on 1 / C of the elements.
+def floor_mean_steps(channels):
+    return 2.0 / channels
+
+
+FLOOR_REL = 2e-6                # fp32 quantities (a few dozen fp32 roundings)
+CAP_MAX_STEPS = 16.0
+CAP_SHARE = 0.03
+
+
+def steps(got, ref):
+    ref = np.asarray(ref, dtype=np.float64)
+    rms = np.sqrt(np.mean(ref ** 2))
+    return np.abs(np.asarray(got, dtype=np.float64) - ref) / (2.0 ** -8 * np.maximum(np.abs(ref), rms))
+
+
+def bf16_stats(got, ref):
+    s = steps(got, ref)
+    return {"max": float(s.max()), "share": float(np.mean(s > 1.0)), "mean": float(s.mean())}
+
+
+def rel_stats(got, ref, scale=None):
+    ref = np.asarray(ref, dtype=np.float64)
+    if scale is None:
+        scale = np.sqrt(np.mean(ref ** 2))
+    e = np.abs(np.asarray(got, dtype=np.float64) - ref) / scale
+    return {"max": float(e.max()), "mean": float(e.mean())}
+
+
+def accept(got, ref, ref32, kind="bf16", scale=None):
+    """-> (ok, report).  kind "bf16": the step metric with its three statistics and the caps; "rel": an fp32 quantity.
+    report = {"got": stats, "d_ref": stats, "bound": stats, "why": [reasons for a rejection]}."""
+    got, ref, ref32 = (np.asarray(v, dtype=np.float64) for v in (got, ref, ref32))
+    assert got.shape == ref.shape == ref32.shape, (got.shape, ref.shape, ref32.shape)
+    why = []
+    if not np.isfinite(got).all():
+        why.append("non-finite values")
+        got = np.nan_to_num(got, nan=1e30, posinf=1e30, neginf=-1e30)
+    if kind == "bf16":
+        st, d = bf16_stats(got, ref), bf16_stats(ref32, ref)
+        bound = {"max": max(FACTOR * d["max"], FLOOR_MAX_STEPS), "share": max(FACTOR * d["share"], FLOOR_SHARE),
+                 "mean": max(FACTOR * d["mean"], floor_mean_steps(ref.shape[-1]))}
+        if bound["max"] > CAP_MAX_STEPS or bound["share"] > CAP_SHARE:
+            why.append(f"VACUOUS: {FACTOR:g} x d_ref (max {d['max']:.3g} steps, share {d['share']:.3g}) is beyond the caps")
+        if st["max"] > CAP_MAX_STEPS:
+            why.append(f"cap: an element is {st['max']:.3g} steps off (> {CAP_MAX_STEPS:g})")
+        if st["share"] > CAP_SHARE:
+            why.append(f"cap: {st['share']:.3g} of the elements are beyond one step (> {CAP_SHARE:g})")
+    else:
+        st, d = rel_stats(got, ref, scale), rel_stats(ref32, ref, scale)
+        bound = {k: max(FACTOR * d[k], FLOOR_REL) for k in ("max", "mean")}
+    for k, b in bound.items():
+        if st[k] > b:
+            why.append(f"{k} {st[k]:.4g} > {b:.4g} (= max({FACTOR:g} x d_ref {d[k]:.4g}, floor))")
+    return not why, {"got": st, "d_ref": d, "bound": bound, "why": why}
+
+
+def fmt(name, rep):
+    f = lambda s: " ".join(f"{k}={v:.3g}" for k, v in s.items())
+    return f"{name:28s} got[{f(rep['got'])}]  d_ref[{f(rep['d_ref'])}]" + ("   REJECTED: " + "; ".join(rep["why"]) if rep["why"] else "")
+
+
+def make_inputs(angle_bins, batch, seed, blocks=3, keeps=(0.9, 0.95, 0.9)):
+    """Lidar states (batch, angle_bins + 2) fp32 and explicit DropPath factors (blocks, batch) for the bf16 tests: in every
+    block neighbouring samples get different factors, cycling through kept-and-rescaled (1 / keep), dropped (0) and
+    untouched (1) with a different phase per block, so a factor taken from the wrong sample always shows (a batch of two
+    alternates between the first two)."""
+    rng = np.random.default_rng(seed)
+    st = np.empty((batch, angle_bins + 2), dtype=np.float32)
+    st[:, :angle_bins] = rng.uniform(0.2, 3.9, size=(batch, angle_bins))
+    st[:, angle_bins:] = rng.uniform(-3, 3, size=(batch, 2))
+    st[batch // 2, 7] = 9.0                                           # > 8: zeroed in place by the forward
+    scale = np.empty((blocks, batch), dtype=np.float32)
+    for i in range(blocks):
+        cycle = np.array([1.0 / keeps[i % len(keeps)], 0.0, 1.0], dtype=np.float32)[:min(batch, 3)]
+        scale[i] = cycle[(np.arange(batch) + i) % len(cycle)]
+    return st, scale

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libporl_hip.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # every symbol include/porl_hip.h declares (tests check the .so exports exactly these)
 SYMBOLS = [
@@ -32,6 +32,7 @@ SYMBOLS = [
     "porl_enc_create", "porl_enc_destroy", "porl_enc_param_floats", "porl_enc_stat_floats",
     "porl_enc_workspace_floats", "porl_enc_tensors", "porl_enc_norms", "porl_enc_blocks",
     "porl_enc_tensor_info", "porl_enc_norm_info", "porl_enc_bind", "porl_enc_weights_changed", "porl_enc_forward",
+    "porl_enc_tap_info",
 ]
 
 
@@ -205,6 +206,7 @@ def _declare(lib):
         getattr(lib, name).restype = i32
     lib.porl_enc_tensor_info.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i64), C.c_char_p, i32]
     lib.porl_enc_norm_info.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.c_char_p, i32]
+    lib.porl_enc_tap_info.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]
     lib.porl_enc_bind.argtypes = [vp, vp, vp, vp]
     lib.porl_enc_weights_changed.argtypes = [vp]
     lib.porl_enc_forward.argtypes = [vp, vp, i64, i32, i32, vp, vp, i64, vp]

@@ -286,6 +286,37 @@ class FasterNet(nn.Module):
 
     forward_cls = forward
 
+    TAP_NAMES = ("stages.0", "stages.2", "pooled", "avgpool_pre_head")
+
+    def tap_info(self, which):
+        """(offset in workspace floats, rows per sample, columns, bytes per element) of tap `which` (index or name)."""
+        if isinstance(which, str):
+            which = self.TAP_NAMES.index(which)
+        off, rps, cols, eb = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        N.check(self._lib.porl_enc_tap_info(self._h, int(which), C.byref(off), C.byref(rps), C.byref(cols), C.byref(eb)),
+                "porl_enc_tap_info")
+        return off.value, rps.value, cols.value, eb.value
+
+    def taps(self, batch):
+        """Intermediate results of the last forward of `batch` samples, as views into the workspace (NHWC: one row per
+        position): "stages.0" (batch * P1, E) and "stages.2" (batch * P2, 2E), bf16 when the bf16-activation branch ran
+        and fp32 otherwise; "pooled" (batch, 2E) and "avgpool_pre_head" (batch, feature_dim), fp32.  Read-only by
+        intent, and valid until the next forward overwrites them."""
+        if self._workspace is None:
+            raise RuntimeError("taps() before the first forward")
+        if not 1 <= batch <= self._cfg.max_batch:
+            raise RuntimeError(f"batch {batch} outside 1..{self._cfg.max_batch}")
+        out = {}
+        for i, name in enumerate(self.TAP_NAMES):
+            off, rps, cols, eb = self.tap_info(i)
+            n = batch * rps * cols
+            if eb == 2:
+                v = self._workspace[off:off + (n + 1) // 2].view(torch.bfloat16)[:n]
+            else:
+                v = self._workspace[off:off + n]
+            out[name] = v.view(batch * rps, cols)
+        return out
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):

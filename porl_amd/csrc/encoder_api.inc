@@ -78,6 +78,14 @@ int64_t enc_ws(porl_enc* h, int64_t n) {
   return off;
 }
 
+// The forward's two branch predicates, shared with porl_enc_tap_info so the query cannot drift from what ran.
+// sparse patch embedding: straight from the lidar state (weight + one patch row of masks fit in LDS)
+bool enc_sparse_patch(const porl_enc* h) {
+  return h->E <= PE_MAX_E && !h->tune.enc_dense_patch && (size_t)PE_K * h->E * sizeof(float) + (size_t)h->P1 * 12 <= 150 * 1024;
+}
+// bf16-activation mode: needs the sparse patch embedding (it writes bf16 directly); otherwise the bf16-operand mode
+bool enc_fused16(const porl_enc* h) { return h->bf16_fused && enc_sparse_patch(h) && !h->tune.enc_bf16_operands_only; }
+
 inline unsigned sweep_blocks(long items) { return (unsigned)std::min<long>((items + 255) / 256, 256L * 32); }
 
 // (rows, K) x (N, K)^T over position rows, split into problems whose operands stay below the 2 GiB reach
@@ -454,6 +462,21 @@ int porl_enc_norm_info(const porl_enc* h, int32_t index, int64_t* mean_offset, i
   return PORL_OK;
 }
 
+int porl_enc_tap_info(const porl_enc* h, int32_t which, int64_t* offset_floats, int64_t* rows_per_sample, int32_t* cols,
+                      int32_t* elem_bytes) {
+  if (!h) PORL_FAIL(PORL_ERR_INVALID, "null engine");
+  if (which < 0 || which >= PORL_ENC_TAPS) PORL_FAIL(PORL_ERR_INVALID, "tap index out of range (0..%d)", PORL_ENC_TAPS - 1);
+  if (!offset_floats || !rows_per_sample || !cols || !elem_bytes) PORL_FAIL(PORL_ERR_INVALID, "null output pointer");
+  const int act_bytes = enc_fused16(h) ? 2 : 4;
+  switch (which) {
+    case PORL_ENC_TAP_STAGE1: *offset_floats = h->ws_x1; *rows_per_sample = h->P1; *cols = h->E; *elem_bytes = act_bytes; break;
+    case PORL_ENC_TAP_STAGE2: *offset_floats = h->ws_x2; *rows_per_sample = h->P2; *cols = h->E2; *elem_bytes = act_bytes; break;
+    case PORL_ENC_TAP_POOLED: *offset_floats = h->ws_pool; *rows_per_sample = 1; *cols = h->E2; *elem_bytes = 4; break;
+    default: *offset_floats = h->ws_feat; *rows_per_sample = 1; *cols = h->cfg.feature_dim; *elem_bytes = 4; break;
+  }
+  return PORL_OK;
+}
+
 int porl_enc_bind(porl_enc* h, float* params, float* bn_stats, float* workspace) {
   if (!h || !params || !bn_stats || !workspace) PORL_FAIL(PORL_ERR_INVALID, "null buffer");
   if (!aligned16(params) || !aligned16(bn_stats) || !aligned16(workspace))
@@ -518,10 +541,8 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
 
   float* x1 = W + h->ws_x1;
   float* x2 = W + h->ws_x2;
-  const bool sparse_patch = E <= PE_MAX_E && !h->tune.enc_dense_patch &&
-                            (size_t)PE_K * E * sizeof(float) + (size_t)h->P1 * 12 <= 150 * 1024;
-  // bf16-activation mode: needs the sparse patch embedding (it writes bf16 directly); otherwise the bf16-operand mode
-  const bool fused16 = h->bf16_fused && sparse_patch && !h->tune.enc_bf16_operands_only;
+  const bool sparse_patch = enc_sparse_patch(h);
+  const bool fused16 = enc_fused16(h);
   if (sparse_patch) {
     // PatchEmbed + its BatchNorm straight from the lidar state: only the ~6 % non-empty patches are convolved
     // (statistics first, then every position is written once, already normalised); no costmap image at all

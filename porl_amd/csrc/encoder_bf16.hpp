@@ -14,8 +14,9 @@
 // an implicit GEMM on the bf16 matrix pipe (9 taps x C/4 input channels), the 2x2s2 PatchMerging a gathered-operand
 // product with its weight walked tap by tap through LDS.  BatchNorm statistics, scale/shift, the patch embedding's
 // arithmetic, the pooled head and everything after it stay fp32; accumulation is fp32 everywhere.
-// fp32 (360x256) remains the parity path: this mode has no reference counterpart and its tolerance is this build's
-// (tests/test_fasternet_gpu.py, tests/test_config5_gpu.py).
+// fp32 (360x256) remains the parity path: this mode has no reference counterpart.  Every rounding to bf16 in this file
+// is mirrored by oracle/fasternet_oracle.py:forward_faithful, and tests/test_encoder_bf16_gpu.py holds the stage outputs
+// to it per position (porl_enc_tap_info); move a rounding point here and the oracle has to move with it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -186,6 +186,24 @@ int main() {
   if (porl_enc_param_floats(e) != 1032960 + 0 && porl_enc_param_floats(e) < 1032960) { ++g_bad; std::fprintf(stderr, "encoder parameter count\n"); }
   if (porl_enc_tensors(e) <= 0 || porl_enc_norms(e) != 5 || porl_enc_blocks(e) != 3 || porl_enc_workspace_floats(e) <= 0) ++g_bad;
   { int64_t off, n; char name[128]; REJECT(porl_enc_tensor_info(e, 10000, &off, &n, name, 128)); ACCEPT(porl_enc_tensor_info(e, 0, &off, &n, name, 128)); }
+  {
+    int64_t off = -1, rps = -1; int32_t cols = -1, eb = -1;
+    REJECT(porl_enc_tap_info(nullptr, 0, &off, &rps, &cols, &eb));
+    REJECT(porl_enc_tap_info(e, -1, &off, &rps, &cols, &eb));
+    REJECT(porl_enc_tap_info(e, PORL_ENC_TAPS, &off, &rps, &cols, &eb));
+    REJECT(porl_enc_tap_info(e, 0, nullptr, &rps, &cols, &eb));
+    REJECT(porl_enc_tap_info(e, 0, &off, nullptr, &cols, &eb));
+    REJECT(porl_enc_tap_info(e, 0, &off, &rps, nullptr, &eb));
+    REJECT(porl_enc_tap_info(e, 0, &off, &rps, &cols, nullptr));
+    if (off != -1 || rps != -1 || cols != -1 || eb != -1) { ++g_bad; std::fprintf(stderr, "a rejected tap query wrote an output\n"); }
+    const int64_t want_rows[PORL_ENC_TAPS] = {(ec.n_ang / 4) * (ec.n_dist / 4), (ec.n_ang / 8) * (ec.n_dist / 8), 1, 1};
+    const int32_t want_cols[PORL_ENC_TAPS] = {ec.embed_dim, 2 * ec.embed_dim, 2 * ec.embed_dim, ec.feature_dim};
+    for (int w = 0; w < PORL_ENC_TAPS; ++w) {                     // ec asks for the bf16-activation mode: stage taps are bf16
+      ACCEPT(porl_enc_tap_info(e, w, &off, &rps, &cols, &eb));
+      if (off < 0 || off % 4 || off + ec.max_batch * rps * cols > porl_enc_workspace_floats(e) || rps != want_rows[w] ||
+          cols != want_cols[w] || eb != (w < 2 ? 2 : 4)) { ++g_bad; std::fprintf(stderr, "tap %d layout\n", w); }
+    }
+  }
   REJECT(porl_enc_forward(e, x, 362, 4, 1, nullptr, x, 256, nullptr));      // unbound
   REJECT(porl_enc_bind(e, nullptr, x, x));
   porl_enc_destroy(e);

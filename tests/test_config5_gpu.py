@@ -11,7 +11,9 @@ input), batch=512, bf16" — exercised at its full batch (VERDICT r2, next-round
 What pins what: the reference can only rasterise 360x256 (util/costmap.py:12,24) and has no bf16 path, so neither (i)
 nor (ii) has a reference golden — "parity unpinned" for those two modes beyond this chain: the oracle is pinned to the
 reference at 360x256 / fp32 (tests/test_oracle_golden.py), the 84x84 oracle is that oracle with the two geometry
-constants replaced, and the HIP fp32 path is compared with it here at full batch.
+constants replaced, and the HIP fp32 path is compared with it here at full batch.  The bf16 KERNELS are pinned per
+position elsewhere: tests/test_encoder_bf16_gpu.py compares the stage outputs of this configuration (84x84, B=512) with
+a bf16-faithful oracle at a few bf16 steps; the bounds below look at pooled features and what follows from them.
 
 bf16 bound (this build's, stated): features within 3e-2 of the largest fp32 feature magnitude; losses within 2e-2
 relative; parameters after three Adam steps within 6.2e-4 (Adam's first steps move a weight by ~lr = 1e-4 whatever the
