@@ -17,11 +17,12 @@ What is pinned:
   fasternet_*: FasterNet(3, 256).forward_cls (/root/reference/agent/fasternet.py:428-438) in eval mode and in
             train mode (batch-stat BatchNorm, running-stat update, DropPath masks replayed from the seed)
   sorl_enc_*: SORL.update with the FasterNet backbone (/root/reference/agent/sorl.py:78-128)
+  *_head_*: one QRDQNTrainer.learn / C51Trainer.learn on table networks: loss and dL/d(network output) of the loss heads
   per_*   : PrioritizedReplayBuffer.add/sample/update_priorities under random.seed; per_trainer_*: PERTrainer.learn; dqn_* / ddqn_*: DQNTrainer.learn / DDQNTrainer.learn; dddqn_*: DDDQNTrainer.learn on DuelingQNetwork
             (/root/reference/src/porl/train/dqn_per_trainer.py:67-123)
             (/root/reference/src/porl/buffer/prioritized_replay_buffer.py:36-108, sum_tree.py:4-77)
 
-Usage:  PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [dddqn] </dev/null
+Usage:  PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden.py [dddqn|iqn|heads] </dev/null
 """
 from __future__ import annotations
 
@@ -824,6 +825,102 @@ def gen_iqn(name, S=9, A=5, E=16, H=64, B=48, K=4, NP=8, NPP=6, seed_model=9, se
     print(f"{name}: loss={losses}")
 
 
+class _TableNet(torch.nn.Module):
+    """Stand-in network for the loss-head goldens: one (rows, A, N) parameter, and the "state" carries the row index in its
+    first column, so the trainer's forward passes return chosen tables and, after learn(), `table.grad` is the reference's
+    own dL/d(network output).  log_probs: end in log_softmax over the last axis, as the reference's categorical network does."""
+
+    def __init__(self, table, log_probs=False):
+        super().__init__()
+        self.table = torch.nn.Parameter(torch.from_numpy(table.copy()))
+        self.log_probs = log_probs
+
+    def forward(self, x):
+        out = self.table[x[:, 0].long()]
+        return torch.log_softmax(out, dim=-1) if self.log_probs else out
+
+    def get_mean_q_values(self, x):
+        return self.forward(x).mean(dim=2)
+
+
+class _OneBatch:
+    def __init__(self, c):
+        B = len(c["rew"])
+        rows = torch.arange(B, dtype=torch.float32)[:, None]
+        self.batch = (rows, torch.from_numpy(c["actions"]), torch.from_numpy(c["rew"]), rows + B, torch.from_numpy(c["done"]))
+
+    def sample(self, batch_size):
+        assert batch_size == self.batch[0].shape[0]
+        return self.batch
+
+
+def _head_trainer(cls, c, online_rows, target_rows, log_probs, gamma):
+    """A hand-built reference trainer on table networks: rows [0, B) answer `states`, rows [B, 2B) answer `next_states`.
+    SGD with lr = 0 leaves the tables alone, so the gradient of the one learn() call stays readable."""
+    B = len(c["rew"])
+    t = object.__new__(cls)
+    t.q_network = _TableNet(np.concatenate(online_rows), log_probs)
+    t.target_network = _TableNet(np.concatenate(target_rows), log_probs)
+    t.optimizer = torch.optim.SGD(t.q_network.parameters(), lr=0.0)
+    t.replay_buffer, t.batch_size, t.gamma, t.device = _OneBatch(c), B, gamma, torch.device("cpu")
+    return t
+
+
+def gen_qr_head(name, NQ, B=37, A=4, kappa=0.6):
+    """QRDQNTrainer.learn (src/porl/train/qr_dqn_trainer.py:97-222), one call on table networks: scalar loss and the
+    reference's own gradient with respect to the online quantiles of `states`."""
+    _stub_cql_imports()
+    from porl.train.qr_dqn_trainer import QRDQNTrainer
+    from oracle import dist_cases as D
+    c = D.qr_case(NQ, A, B, seed="golden")
+    t = _head_trainer(QRDQNTrainer, c, (c["z_cur"], c["z_next_online"]), (np.zeros_like(c["z_cur"]), c["z_next_target"]),
+                      False, D.GAMMA)
+    t.num_quantiles, t.kappa = NQ, kappa
+    i = torch.arange(0, NQ, dtype=torch.float32)
+    t.tau = ((2 * i + 1) / (2 * NQ)).unsqueeze(0)
+    loss = QRDQNTrainer.learn(t)
+    grad = t.q_network.table.grad.numpy()
+    assert not grad[B:].any() and np.array_equal(t.q_network.table.detach().numpy()[:B], c["z_cur"])
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), z_cur=c["z_cur"], z_next_online=c["z_next_online"],
+                        z_next_target=c["z_next_target"], actions=c["actions"], rew=c["rew"], done=c["done"],
+                        gamma=np.float64(D.GAMMA), kappa=np.float64(kappa), loss=np.float64(loss), grad=grad[:B].copy())
+    print(f"{name}: loss={loss}")
+
+
+def gen_c51_head(name, NA, B=37, A=4, v_min=-10.0, v_max=10.0):
+    """C51Trainer.learn (src/porl/train/c51_trainer.py:52-174), one call on table networks whose forward ends in
+    log_softmax: scalar loss and the reference's gradient with respect to the online PRE-softmax outputs of `states`.
+    The rewards of the case spread over half the support's width around its middle, so both clamps occur."""
+    _stub_cql_imports()
+    from porl.train.c51_trainer import C51Trainer
+    from oracle import dist_cases as D
+    c = D.c51_case(NA, A, B, (v_min, v_max), seed="golden")
+    t = _head_trainer(C51Trainer, c, (c["logits_cur"], np.zeros_like(c["logits_cur"])),
+                      (np.zeros_like(c["logits_cur"]), c["logits_next_target"]), True, D.GAMMA)
+    t.atom_size, t.v_min, t.v_max = NA, v_min, v_max
+    t.delta_z = (v_max - v_min) / (NA - 1)
+    t.support = torch.linspace(v_min, v_max, NA)
+    assert np.array_equal(t.support.numpy(), c["support"])
+    tz = c["rew"][:, None] + D.GAMMA * c["support"][None] * (1 - c["done"][:, None])
+    assert (tz < v_min).any() and (tz > v_max).any()
+    loss = C51Trainer.learn(t)
+    grad = t.q_network.table.grad.numpy()
+    assert not grad[B:].any()
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), logits_cur=c["logits_cur"], logits_next_target=c["logits_next_target"],
+                        actions=c["actions"], rew=c["rew"], done=c["done"], support=c["support"], gamma=np.float64(D.GAMMA),
+                        v_min=np.float64(v_min), v_max=np.float64(v_max), loss=np.float64(loss), grad=grad[:B].copy())
+    print(f"{name}: loss={loss}")
+
+
+HEAD_GOLDENS = {"qr_head_n51": lambda n: gen_qr_head(n, 51), "qr_head_n200": lambda n: gen_qr_head(n, 200),
+                "c51_head_n51": lambda n: gen_c51_head(n, 51), "c51_head_n101": lambda n: gen_c51_head(n, 101)}
+
+
+def gen_heads():
+    for name, fn in HEAD_GOLDENS.items():
+        fn(name)
+
+
 def sub_dict(d, prefix):
     return {k[len(prefix):]: v for k, v in d.items() if k.startswith(prefix)}
 
@@ -832,7 +929,7 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     if len(sys.argv) > 1:                      # `gen_golden.py dddqn`: (re)generate one fixture family only
-        {"dddqn": lambda: gen_dddqn("dddqn_s10_a6"), "iqn": lambda: gen_iqn("iqn_s9_a5")}[sys.argv[1]]()
+        {"dddqn": lambda: gen_dddqn("dddqn_s10_a6"), "iqn": lambda: gen_iqn("iqn_s9_a5"), "heads": gen_heads}[sys.argv[1]]()
         return
     # POR — small, fully stored
     gen_por("por_s60_h64_b32", S=60, H=64, L=2, layer_norm=False, B=32, K=5, full=True)
@@ -870,6 +967,7 @@ def main():
     gen_c51("c51_s9_a5_n21")
     gen_iqn_loss("iqn_quantile_huber")
     gen_iqn("iqn_s9_a5")
+    gen_heads()
 
 
 if __name__ == "__main__":
