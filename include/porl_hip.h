@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define PORL_ABI_VERSION 9
+#define PORL_ABI_VERSION 10
 #define PORL_MAX_HIDDEN 8
 
 #define PORL_OK 0
@@ -527,6 +527,26 @@ int porl_per_update(double* tree, int64_t capacity, const int64_t* tree_idx, con
                     double eps, double alpha, int32_t* stamp, void* stream);
 int porl_per_sample(const double* tree, int64_t capacity, const double* u, int32_t batch, int64_t n_entries,
                     double beta, int64_t* out_idx, double* out_prio, float* out_w, void* stream);
+
+/* The same three operations shaped for the online loop (dqn_per_trainer.py:127-175), one launch each; every tree value,
+ * tree index and weight is bit-equal to what the two calls above give for the same inputs.
+ * porl_per_record: memory.add of one transition into data slot `slot`: the row (host floats, state_dim <=
+ *   PORL_RECORD_MAX_STATE each, else PORL_ERR_UNSUPPORTED) is copied into the kernel's arguments at launch and written
+ *   to the five arrays of `store` (store->capacity == capacity), the slot's leaf becomes (|td_error| + eps)^alpha and
+ *   its ancestors are recomputed, leaf to root.
+ * porl_per_sample_slots: porl_per_sample without the priorities; also out_slots = out_idx - (capacity - 1) (the rows
+ *   porl_qnet_learn_variant gathers) and out_wmean[0] = fp32 of (fp64 sum of the raw weights, i = 0..batch-1) / max /
+ *   batch — the uniform_weight of the reference's (B,1)x(B,) loss.  `scratch`: batch doubles.
+ * porl_per_update_f32: porl_per_update in one launch on fp32 |TD errors| (widened to fp64 as they are read), e.g.
+ *   the td_abs of porl_qnet_variant; tree indices outside the leaves are ignored; `stamp` as above. */
+int porl_per_record(double* tree, int64_t capacity, int64_t slot, double td_error, double eps, double alpha,
+                    const float* state, const float* next_state, int32_t state_dim, int64_t action, float reward,
+                    float done, const porl_qnet_mirror* store, void* stream);
+int porl_per_sample_slots(const double* tree, int64_t capacity, const double* u, int32_t batch, int64_t n_entries,
+                          double beta, int64_t* out_idx, int64_t* out_slots, float* out_w, float* out_wmean,
+                          double* scratch, void* stream);
+int porl_per_update_f32(double* tree, int64_t capacity, const int64_t* tree_idx, const float* td_abs, int32_t n,
+                        double eps, double alpha, int32_t* stamp, void* stream);
 
 /* Experiment knobs (scheduling only, never the mathematics).  "gemm_lds_pad": extra dynamic LDS bytes per GEMM block,
  * limiting how many blocks share a CU.  "qnet_fused": 0 forces the multi-launch CQL path.  porl_tune_set sets the process

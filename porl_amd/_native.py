@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libporl_hip.so")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # every symbol include/porl_hip.h declares (tests check the .so exports exactly these)
 SYMBOLS = [
@@ -22,6 +22,7 @@ SYMBOLS = [
     "porl_iql_value_backward", "porl_iql_value_apply", "porl_iql_policy_forward", "porl_iql_policy_backward",
     "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_only_forward", "porl_iql_policy_only_step", "porl_iql_policy_prefetch", "porl_iql_forward_value", "porl_iql_forward_policy",
     "porl_gemm_f32", "porl_adam_ema", "porl_ema", "porl_softmax_mask", "porl_gather_rows", "porl_sample_indices", "porl_epoch_indices", "porl_per_update", "porl_per_sample",
+    "porl_per_record", "porl_per_sample_slots", "porl_per_update_f32",
     "porl_prof_enable", "porl_prof_read", "porl_tune_set", "porl_tune_set_ptr", "porl_state2costmap",
     "porl_signal_create", "porl_signal_destroy", "porl_signal_write", "porl_signal_wait_ge", "porl_iql_update_pipelined",
     "porl_qnet_create", "porl_qnet_destroy", "porl_qnet_param_floats", "porl_qnet_tensors",
@@ -142,6 +143,9 @@ def _declare(lib):
     lib.porl_epoch_indices.argtypes = [i64, i64, i32, C.c_uint64, C.c_uint64, i64, vp, vp]
     lib.porl_per_update.argtypes = [vp, i64, vp, vp, i32, f64, f64, vp, vp]
     lib.porl_per_sample.argtypes = [vp, i64, vp, i32, i64, f64, vp, vp, vp, vp]
+    lib.porl_per_record.argtypes = [vp, i64, i64, f64, f64, f64, vp, vp, i32, i64, f32, f32, C.POINTER(QnetMirror), vp]
+    lib.porl_per_sample_slots.argtypes = [vp, i64, vp, i32, i64, f64, vp, vp, vp, vp, vp, vp]
+    lib.porl_per_update_f32.argtypes = [vp, i64, vp, vp, i32, f64, f64, vp, vp]
     lib.porl_tune_set.argtypes = [C.c_char_p, C.c_int]
     lib.porl_iql_tune_set.argtypes = [vp, C.c_char_p, C.c_int]
     lib.porl_tune_set_ptr.argtypes = [C.c_char_p, vp]

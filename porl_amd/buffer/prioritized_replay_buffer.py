@@ -13,9 +13,15 @@ recomputed from their children instead of accumulating rounded differences (sums
 sampled index can differ from the reference only when s falls within that distance of a boundary); the reference's
 "resample from the full range when an empty slot is hit" branch is not needed because empty leaves carry zero
 priority.  `add` queues on the host and is flushed in one batch before the next `sample`/`update_priorities`.
+
+For the online loop (train/online.py) three one-launch forms sit beside them, bit-equal in everything they write:
+`record` (= `add` + flush of that transition, the row carried in the kernel's arguments), `sample_slots` (= `sample`
+without the gathers: data slots for the step kernel, weights, their mean, tree indices) and `update_priorities_device`
+(= `update_priorities` on a device fp32 tensor, e.g. the step kernel's |TD errors|).
 """
 from __future__ import annotations
 
+import ctypes as C
 import random
 
 import numpy as np
@@ -39,6 +45,8 @@ class PrioritizedReplayBuffer:
         self._store = None
         self.data_pointer, self.n_entries = 0, 0
         self._pending = []                 # (slot, td_error, state, action, reward, next_state, done)
+        self._store_c = None               # the store's arrays as porl_qnet_mirror (record)
+        self._u = None                     # sample_slots: staging ring of the uniforms + the raw-weight scratch
 
     # -- storage ---------------------------------------------------------------------------------------
     def _alloc(self, state):
@@ -121,6 +129,94 @@ class PrioritizedReplayBuffer:
         if idx.numel() != td.numel():
             raise ValueError("tree_indices and td_errors differ in length")
         self._update(idx, td)
+
+    # -- one-launch forms for the online loop (csrc/per_online.hpp) ---------------------------------------
+    _RING = 8
+
+    def record(self, td_error, *experience):
+        """`add` whose transition reaches the store and the tree by one launch (porl_per_record), nothing left pending;
+        earlier `add`s are flushed first.  False (and a plain `add`) when the state is too wide for the arguments."""
+        state, action, reward, next_state, done = experience
+        if self._store is None:
+            self._alloc(state)
+        st = self._store
+        sdim = st["states"].shape[1]
+        from ..train.cql_trainer import QnetEngine
+        if sdim > QnetEngine.RECORD_MAX_STATE:                 # PORL_RECORD_MAX_STATE: the row rides in the kernel's arguments
+            self.add(td_error, *experience)
+            return False
+        if self._pending:
+            self._flush()
+        state = np.ascontiguousarray(state, dtype=np.float32).reshape(-1)
+        next_state = np.ascontiguousarray(next_state, dtype=np.float32).reshape(-1)
+        if state.size != sdim or next_state.size != sdim:
+            raise ValueError(f"state of {state.size} / {next_state.size} values in a buffer of {sdim}-wide rows")
+        if self._store_c is None:
+            self._store_c = N.QnetMirror(*[C.c_void_p(st[k].data_ptr()) for k in
+                                           ("states", "next_states", "actions", "rewards", "dones")], self.capacity)
+        N.check(N.lib().porl_per_record(N.ptr(self.tree), self.capacity, self.data_pointer, float(td_error), self.epsilon,
+                                        self.alpha, state.ctypes.data, next_state.ctypes.data, sdim, int(action),
+                                        float(reward), float(done), C.byref(self._store_c),
+                                        N.current_stream_ptr(self.device)), "porl_per_record")
+        self.data_pointer += 1
+        if self.data_pointer >= self.capacity:
+            self.data_pointer = 0
+        if self.n_entries < self.capacity:
+            self.n_entries += 1
+        return True
+
+    def sample_slots(self, batch_size):
+        """`sample` without the gathers, one launch (porl_per_sample_slots) -> (slots, is_weights, wmean, tree_idx):
+        int64 data slots (= tree_idx - (capacity - 1)) for a kernel that reads the store's rows itself, the fp32
+        normalised weights, their mean as a 1-element fp32 tensor, the int64 tree indices.  Same beta / frame_count
+        bookkeeping and the same batch_size draws from `random`, in the same order, as `sample`."""
+        if self._pending:
+            self._flush()
+        if self.n_entries < 1:
+            raise ValueError("cannot sample from an empty buffer")
+        B = int(batch_size)
+        self.beta = np.min([1.0, self.beta_start + self.frame_count * (1.0 - self.beta_start) / self.beta_frames])
+        self.frame_count += 1
+        if self._u is None or self._u["host"].shape[1] != B:
+            self._u = dict(host=torch.zeros(self._RING, B, dtype=torch.float64).pin_memory(),
+                           dev=torch.zeros(self._RING, B, dtype=torch.float64, device=self.device),
+                           raw=torch.zeros(B, dtype=torch.float64, device=self.device), ev=[None] * self._RING, k=0)
+        r = self._u
+        k = r["k"]
+        r["k"] = (k + 1) % self._RING
+        # a staging slot is rewritten only after its copy has completed
+        if r["ev"][k] is not None:
+            r["ev"][k].synchronize()
+        else:
+            r["ev"][k] = torch.cuda.Event()
+        # random.uniform(a, b) == a + (b - a) * random.random(): one draw per segment, in segment order
+        rnd = random.random
+        r["host"][k].numpy()[:] = [rnd() for _ in range(B)]
+        u = r["dev"][k]
+        u.copy_(r["host"][k], non_blocking=True)
+        r["ev"][k].record(torch.cuda.current_stream(self.device))
+        idx = torch.empty(2, B, dtype=torch.int64, device=self.device)             # tree indices | data slots
+        w = torch.empty(B + 1, dtype=torch.float32, device=self.device)             # weights | their mean
+        N.check(N.lib().porl_per_sample_slots(N.ptr(self.tree), self.capacity, N.ptr(u), B, self.n_entries, float(self.beta),
+                                              N.ptr(idx[0]), N.ptr(idx[1]), N.ptr(w), C.c_void_p(w.data_ptr() + 4 * B),
+                                              N.ptr(r["raw"]), N.current_stream_ptr(self.device)), "porl_per_sample_slots")
+        return idx[1], w[:B], w[B:], idx[0]
+
+    def update_priorities_device(self, tree_indices, td_errors):
+        """`update_priorities` for device tensors as they are — int64 tree indices, fp32 TD errors — in one launch
+        (porl_per_update_f32); the tree comes out bit-equal to update_priorities(tree_indices, td_errors)."""
+        if self._pending:
+            self._flush()
+        for name, x, dt in (("tree_indices", tree_indices, torch.int64), ("td_errors", td_errors, torch.float32)):
+            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
+                raise ValueError(f"{name}: need a contiguous {dt} tensor on {self.device}")
+        if tree_indices.numel() != td_errors.numel():
+            raise ValueError("tree_indices and td_errors differ in length")
+        if tree_indices.numel() == 0:
+            return
+        N.check(N.lib().porl_per_update_f32(N.ptr(self.tree), self.capacity, N.ptr(tree_indices), N.ptr(td_errors),
+                                            tree_indices.numel(), self.epsilon, self.alpha, N.ptr(self._stamp),
+                                            N.current_stream_ptr(self.device)), "porl_per_update_f32")
 
     def __len__(self):
         return self.n_entries

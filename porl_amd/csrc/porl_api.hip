@@ -21,6 +21,7 @@
 #include "per_tree.hpp"
 #include "dist_losses.hpp"
 #include "online.hpp"
+#include "per_online.hpp"
 
 using namespace porl;
 
@@ -1590,7 +1591,7 @@ int porl_per_update(double* tree, int64_t capacity, const int64_t* tree_idx, con
   hipLaunchKernelGGL(per_stamp_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, tree_idx, n, capacity, stamp);
   hipLaunchKernelGGL(per_set_leaves_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, tree, tree_idx, td_error, n, capacity, eps,
                      alpha, stamp);
-  int levels = 0;
+  int levels = 0;                                                        // keep in step with per_levels() below
   for (int64_t v = 2 * capacity - 1; v > 1; v >>= 1) ++levels;          // depth of the deepest leaf
   hipLaunchKernelGGL(per_propagate_kernel, dim3(1), dim3(1024), 0, s, tree, tree_idx, n, levels);
   PORL_HIP(hipGetLastError());
@@ -1604,6 +1605,62 @@ int porl_per_sample(const double* tree, int64_t capacity, const double* u, int32
   DevGuard _dg(device_of(tree));
   PerSampleArgs a{tree, capacity, u, batch, n_entries, beta, out_idx, out_prio, out_w};
   hipLaunchKernelGGL(per_sample_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+// ---- prioritized replay inside the online loop (per_online.hpp) -----------------------------------------------------
+static int per_levels(int64_t capacity) {                               // the loop of porl_per_update above: keep in step
+  int levels = 0;
+  for (int64_t v = 2 * capacity - 1; v > 1; v >>= 1) ++levels;          // depth of the deepest leaf
+  return levels;
+}
+
+int porl_per_record(double* tree, int64_t capacity, int64_t slot, double td_error, double eps, double alpha,
+                    const float* state, const float* next_state, int32_t state_dim, int64_t action, float reward,
+                    float done, const porl_qnet_mirror* store, void* stream) {
+  if (!tree || !state || !next_state || !store || !store->states || !store->next_states || !store->actions ||
+      !store->rewards || !store->dones)
+    PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  if (capacity < 1 || store->capacity != capacity)
+    PORL_FAIL(PORL_ERR_INVALID, "capacity %lld < 1 or the store holds %lld rows", (long long)capacity, (long long)store->capacity);
+  if (state_dim < 1) PORL_FAIL(PORL_ERR_INVALID, "state_dim %d < 1", state_dim);
+  if (state_dim > ONL_MAX_RECORD_S)
+    PORL_FAIL(PORL_ERR_UNSUPPORTED, "state_dim %d > %d: too wide for the kernel arguments", state_dim, ONL_MAX_RECORD_S);
+  if (slot < 0 || slot >= capacity) PORL_FAIL(PORL_ERR_INVALID, "slot %lld outside [0,%lld)", (long long)slot, (long long)capacity);
+  DevGuard _dg(device_of(tree));
+  PerRecordArgs a;
+  a.states = store->states; a.next_states = store->next_states; a.actions = store->actions; a.rewards = store->rewards;
+  a.dones = store->dones; a.tree = tree; a.capacity = capacity; a.slot = slot; a.action = action;
+  a.td_error = td_error; a.eps = eps; a.alpha = alpha; a.reward = reward; a.done = done; a.S = state_dim;
+  memcpy(a.x, state, sizeof(float) * state_dim);
+  memcpy(a.x + state_dim, next_state, sizeof(float) * state_dim);
+  hipLaunchKernelGGL(per_record_kernel, dim3(1), dim3(state_dim > 64 ? 256 : 64), 0, (hipStream_t)stream, a);
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+int porl_per_sample_slots(const double* tree, int64_t capacity, const double* u, int32_t batch, int64_t n_entries,
+                          double beta, int64_t* out_idx, int64_t* out_slots, float* out_w, float* out_wmean,
+                          double* scratch, void* stream) {
+  if (!tree || !u || !out_idx || !out_slots || !out_w || !out_wmean || !scratch) PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  if (capacity < 1 || batch < 1 || n_entries < 1 || n_entries > capacity)
+    PORL_FAIL(PORL_ERR_INVALID, "need capacity >= 1, batch >= 1, 1 <= n_entries <= capacity");
+  DevGuard _dg(device_of(tree));
+  PerSampleSlotsArgs a{tree, capacity, u, batch, n_entries, beta, out_idx, out_slots, out_w, out_wmean, scratch};
+  hipLaunchKernelGGL(per_sample_slots_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+int porl_per_update_f32(double* tree, int64_t capacity, const int64_t* tree_idx, const float* td_abs, int32_t n, double eps,
+                        double alpha, int32_t* stamp, void* stream) {
+  if (!tree || !tree_idx || !td_abs || !stamp) PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  if (capacity < 1 || n < 1) PORL_FAIL(PORL_ERR_INVALID, "need capacity >= 1 and n >= 1");
+  DevGuard _dg(device_of(tree));
+  const int threads = n >= 1024 ? 1024 : (n + 63) / 64 * 64;
+  hipLaunchKernelGGL(per_update_f32_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, tree, tree_idx, td_abs, n, capacity,
+                     eps, alpha, stamp, per_levels(capacity));
   PORL_HIP(hipGetLastError());
   return PORL_OK;
 }

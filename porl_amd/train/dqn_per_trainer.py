@@ -58,7 +58,13 @@ class PERTrainer(CQLTrainer):
 
     def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
         """dqn_per_trainer.py:127-175: memory.add(max_initial_priority, ...) and a learn step once len(memory) >=
-        batch_size; the loop of train/online.py on this trainer's select_action / add / learn."""
+        batch_size; the loop of train/online.py.  On the one-launch step kernel with this class's own learn /
+        select_action / get_action, acting, adding, sampling and the priority write-back take their one-launch forms
+        (online._FastPER); otherwise the loop runs on select_action / memory.add / learn."""
         from . import online
+        cls, fast = type(self), None
+        if cls.learn is PERTrainer.learn and cls._act_for is cls.select_action and cls._greedy_for is cls.get_action and \
+                online.fast_per_ok(self):
+            fast = online._FastPER(self)
         return online.run(self, env, policy, num_episodes, max_steps, self.batch_size, self.memory,
-                          lambda *e: self.memory.add(self.max_initial_priority, *e))
+                          lambda *e: self.memory.add(self.max_initial_priority, *e), fast)

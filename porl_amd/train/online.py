@@ -14,18 +14,27 @@ Fast path (`_Fast`), taken when the network lives on a QnetEngine and the memory
     once: the act record carries the statistics of the step before it, and losses of steps followed by an exploring
     step are parked in a device log, read at the next greedy action or the episode's end.  The logger calls are
     replayed then, in their original order.
-Everything else (PER, IQN, user `policy` callables, networks too large for one workgroup) runs the reference loop on
-the trainer's own select_action / push / learn.
+PER flavour (`_FastPER`, PERTrainer on the one-launch step kernel; dqn_per_trainer.py:127-175): the memory is the
+device-resident PrioritizedReplayBuffer, so
+  * push: PrioritizedReplayBuffer.record — one launch writes the row and the leaf (max_initial_priority) and
+    recomputes the leaf's ancestors; the greedy action reads the row of the store's next_states just recorded;
+  * learn: sample_slots (one copy of the batch's uniforms, drawn from Python's `random` exactly as the reference draws
+    them, one launch for tree walk, weights and their mean) -> the step kernel on rows `slots` (Double-DQN, importance
+    weights or their mean, |TD| out) -> update_priorities_device (one launch); losses deferred as above.
+Everything else (IQN, user `policy` callables, networks too large for one workgroup) runs the reference loop on the
+trainer's own select_action / push / learn.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
+from .. import _native as N
+
 
 class _Fast:
-    def __init__(self, trainer, kind=0, n_sub=1, support=None, learn_rows=None):
-        self.t, self.eng, self.rb = trainer, trainer._engine, trainer.replay_buffer
+    def __init__(self, trainer, kind=0, n_sub=1, support=None, learn_rows=None, memory=None):
+        self.t, self.eng, self.rb = trainer, trainer._engine, trainer.replay_buffer if memory is None else memory
         self.kind, self.n_sub, self.support = kind, n_sub, support
         self.n_act = trainer.action_size
         self.learn_rows = learn_rows               # None: the trainer's own learn()
@@ -40,6 +49,10 @@ class _Fast:
         self.parked = []                           # their loss slots, in log order
         self.in_stats = None                       # loss slot of the newest learn, its value still only in eng.stats
         self.values = []                           # loss per slot (None until read)
+        self._make_ring()
+
+    def _make_ring(self):
+        trainer = self.t
         # minibatch indices: pinned staging ring; a slot is rewritten only after its copy has completed
         self.R = 32
         B = trainer.batch_size
@@ -54,13 +67,16 @@ class _Fast:
         n_stats = 1 if self.in_stats is not None else 0
         kw = dict(kind=self.kind, n_act=self.n_act, n_sub=self.n_sub, support=self.support, n_stats=n_stats)
         if self.state_row is not None:
-            eng.act(self.rec, states=self.rb._mirror["next_states"], row=self.state_row, **kw)
+            eng.act(self.rec, states=self._next_states(), row=self.state_row, **kw)
         else:
             eng.act(self.rec, inline=np.asarray(state, dtype=np.float32).reshape(-1), **kw)
         self.stream.synchronize()
         if n_stats:
             self.resolve(float(self.rec_f[8]))
         return int(self.rec[0])
+
+    def _next_states(self):
+        return self.rb._mirror["next_states"]
 
     def explore(self):
         """An exploring step: park the newest loss (if any) before the next learn overwrites the statistics."""
@@ -92,7 +108,11 @@ class _Fast:
         d.copy_(self.idx_host[k], non_blocking=True)
         self.idx_ev[k].record(self.stream)
         self.learn_rows(d)
-        if t.async_losses:
+        return self._deferred_loss()
+
+    def _deferred_loss(self):
+        """The loss of the step just launched: the device statistics (async_losses) or a slot to be filled later."""
+        if self.t.async_losses:
             return self.eng.stats[:3]
         if self.log is None:
             self.log = torch.zeros(self.max_steps + 1, dtype=torch.float32, device=self.eng.device)
@@ -119,6 +139,45 @@ class _Fast:
             self.calls.append((fn, args))
         else:
             fn(*args)
+
+
+class _FastPER(_Fast):
+    """PERTrainer: the memory is the PrioritizedReplayBuffer; push = record, learn = sample_slots -> step kernel on the
+    store's rows -> fused priority write-back (PERTrainer.learn's arithmetic, launch for launch on the step kernel)."""
+
+    def __init__(self, trainer):
+        super().__init__(trainer, memory=trainer.memory)
+        self.views = None
+
+    def _make_ring(self):
+        pass                                       # no index ring: the slots are drawn on the device (sample_slots)
+
+    def _next_states(self):
+        return self.rb._store["next_states"]
+
+    def push(self, state, action, reward, next_state, done):
+        p = self.rb.data_pointer
+        ok = self.rb.record(self.t.max_initial_priority, state, action, reward, next_state, done)
+        self.state_row = p if ok else None
+
+    def learn(self):
+        t, mem, eng = self.t, self.rb, self.eng
+        B = t.batch_size
+        slots, is_w, wmean, tree_idx = mem.sample_slots(B)
+        if self.views is None:
+            st = mem._store
+            self.views = (st["states"], st["actions"], st["rewards"].view(-1), st["next_states"], st["dones"].view(-1))
+        t.optimizer.step_count += 1
+        g = t.optimizer.param_groups[0]
+        hp = eng.hyper(t.gamma, 0.0, 1.0 / B, t.optimizer.step_count, g["lr"], g["betas"], g["eps"])
+        td_abs = t._td_abs[:B]
+        if t.per_sample_weights:
+            var = N.QnetVariant(1, is_w.data_ptr(), None, td_abs.data_ptr())
+        else:
+            var = N.QnetVariant(1, None, wmean.data_ptr(), td_abs.data_ptr())
+        eng.learn_indexed(hp, *self.views, slots, variant=var)
+        mem.update_priorities_device(tree_idx, td_abs)
+        return self._deferred_loss()
 
 
 class _Loss:
@@ -185,6 +244,23 @@ def run(trainer, env, policy, num_episodes, max_steps, threshold, memory, push, 
     env.close()
     t.logger.close()
     return rewards_history
+
+
+def fast_per_ok(trainer):
+    """The one-launch PER path applies: the trainer's own learn() on the one-launch step kernel, a network the act
+    kernel covers, a device PrioritizedReplayBuffer whose rows fit the record kernel, no gradient exchange."""
+    from ..buffer.prioritized_replay_buffer import PrioritizedReplayBuffer
+    from ..engine import _norm_device
+    eng, mem = getattr(trainer, "_engine", None), trainer.memory
+    if eng is None or eng.device.type != "cuda" or type(mem) is not PrioritizedReplayBuffer or \
+            _norm_device(mem.device) != eng.device or trainer._exchange.active:
+        return False
+    S = eng.cfg.state_dim
+    if mem.state_shape is None or int(np.prod(mem.state_shape)) != S or \
+            S > eng.RECORD_MAX_STATE or S > eng.ACT_MAX_INLINE or trainer.batch_size > trainer._td_abs.numel():
+        return False
+    eng._ensure_bound()
+    return eng.fused and eng.act_ok
 
 
 def fast_ok(trainer):
