@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define PORL_ABI_VERSION 10
+#define PORL_ABI_VERSION 11
 #define PORL_MAX_HIDDEN 8
 
 #define PORL_OK 0
@@ -339,6 +339,30 @@ int porl_qnet_learn_variant(porl_qnet* h, const float* states, int64_t s_rs, con
                             const float* rewards, const float* next_states, int64_t n_rs, const float* dones,
                             const int64_t* idx, int32_t batch, const porl_qnet_hyper* hp,
                             const porl_qnet_variant* variant, void* stream);
+/* One learn step of a distributional trainer (src/porl/train/qr_dqn_trainer.py:97-222, c51_trainer.py:52-174) on the
+ * minibatch { row idx[b] (or b when idx is NULL) of the given replay arrays : b < batch } from one call: gather into the
+ * staging buffers, the forwards as one grouped launch per layer (online net on s with its activations kept, target net
+ * on s', for QR-DQN also the online net on s'), the loss head on the workspace's padded output rows writing
+ * dL/d(output) where the backward chain reads it, stats[0] = batch mean of the row losses (porl_reduce_mean's order),
+ * backward, Adam.  Parameters, Adam moments, row losses and the mean are bit-equal to porl_qnet_load_batch +
+ * porl_qnet_forward_loaded + porl_qr_loss / porl_c51_loss + porl_qnet_backward + porl_qnet_apply + porl_reduce_mean on
+ * the same rows.  hp->gamma, inv_batch (unused: 1/batch is applied), step, lr, adam_*: as porl_qnet_apply.
+ * head: kind PORL_DIST_QR (n_sub quantiles per action, kappa) or PORL_DIST_C51 (n_sub >= 2 atoms, v_min < v_max,
+ * support = n_sub device floats); n_actions * n_sub must equal the engine's outputs, n_sub <= 256.  Every argument is
+ * checked before the first launch. */
+#define PORL_DIST_QR 0
+#define PORL_DIST_C51 1
+typedef struct porl_dist_head {
+  int32_t kind;
+  int32_t n_actions;
+  int32_t n_sub;
+  float kappa;
+  float v_min, v_max;
+  const float* support;
+} porl_dist_head;
+int porl_qnet_dist_learn(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
+                         const float* next_states, int64_t n_rs, const float* dones, const int64_t* idx, int32_t batch,
+                         const porl_qnet_hyper* hp, const porl_dist_head* head, void* stream);
 int porl_qnet_sync_target(porl_qnet* h, void* stream);
 /* q_network(states) (which=0) or target_network(states) (which=1) -> (batch, n_actions) */
 int porl_qnet_forward(porl_qnet* h, int which, const float* states, int64_t s_rs, int32_t batch,

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libporl_hip.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # every symbol include/porl_hip.h declares (tests check the .so exports exactly these)
 SYMBOLS = [
@@ -28,7 +28,7 @@ SYMBOLS = [
     "porl_qnet_create", "porl_qnet_destroy", "porl_qnet_param_floats", "porl_qnet_tensors",
     "porl_qnet_tensor_info", "porl_qnet_workspace_floats", "porl_qnet_bind", "porl_qnet_load_batch",
     "porl_qnet_cql_backward", "porl_qnet_apply", "porl_qnet_learn", "porl_qnet_sync_target",
-    "porl_qnet_forward", "porl_qnet_forward_loaded", "porl_qnet_backward", "porl_qr_loss", "porl_iqn_quantile_huber", "porl_iqn_cos_embed", "porl_iqn_hadamard", "porl_iqn_hadamard_backward", "porl_iqn_select", "porl_iqn_scatter", "porl_iqn_target", "porl_grad_clip", "porl_c51_loss", "porl_reduce_mean", "porl_qnet_penalty", "porl_qnet_learn_indexed", "porl_qnet_one_launch", "porl_qnet_learn_variant", "porl_qnet_can_sample", "porl_qnet_learn_sampled",
+    "porl_qnet_forward", "porl_qnet_forward_loaded", "porl_qnet_backward", "porl_qr_loss", "porl_iqn_quantile_huber", "porl_iqn_cos_embed", "porl_iqn_hadamard", "porl_iqn_hadamard_backward", "porl_iqn_select", "porl_iqn_scatter", "porl_iqn_target", "porl_grad_clip", "porl_c51_loss", "porl_reduce_mean", "porl_qnet_penalty", "porl_qnet_learn_indexed", "porl_qnet_one_launch", "porl_qnet_learn_variant", "porl_qnet_can_sample", "porl_qnet_learn_sampled", "porl_qnet_dist_learn",
     "porl_qnet_record", "porl_qnet_act_ok", "porl_qnet_act",
     "porl_enc_create", "porl_enc_destroy", "porl_enc_param_floats", "porl_enc_stat_floats",
     "porl_enc_workspace_floats", "porl_enc_tensors", "porl_enc_norms", "porl_enc_blocks",
@@ -73,6 +73,11 @@ class QnetHyper(C.Structure):
 class QnetVariant(C.Structure):
     _fields_ = [("double_dqn", C.c_int32), ("is_weights", C.c_void_p), ("uniform_weight", C.c_void_p),
                 ("td_abs", C.c_void_p), ("next_mask", C.c_void_p), ("td_off", C.c_int32)]
+
+
+class DistHead(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_actions", C.c_int32), ("n_sub", C.c_int32), ("kappa", C.c_float),
+                ("v_min", C.c_float), ("v_max", C.c_float), ("support", C.c_void_p)]
 
 
 class QnetMirror(C.Structure):
@@ -173,6 +178,8 @@ def _declare(lib):
     lib.porl_qnet_learn_indexed.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, C.POINTER(QnetHyper), vp]
     lib.porl_qnet_learn_variant.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, C.POINTER(QnetHyper),
                                             C.POINTER(QnetVariant), vp]
+    lib.porl_qnet_dist_learn.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, C.POINTER(QnetHyper),
+                                         C.POINTER(DistHead), vp]
     lib.porl_qnet_one_launch.argtypes = [vp]
     lib.porl_qnet_one_launch.restype = i32
     lib.porl_qnet_can_sample.argtypes = [vp]

@@ -1821,6 +1821,7 @@ struct porl_qnet {
   struct {
     int64_t xs, xn, rew, done, actions;                  // actions: int64 stored in 2 floats each
     int64_t act[PORL_MAX_HIDDEN + 1], tmp[2], dz[2], slab, part_td, part_pen, fslab, total;
+    int64_t tmp2[2], row_loss;                           // porl_qnet_dist_learn: third forward's ping-pong, per-row losses
   } ws;
   // one-launch path (qnet_fused.hpp): every width <= 128, at most QF_MAX_LIN Linear layers, LDS plan fits
   bool fused_ok = false;
@@ -1930,6 +1931,9 @@ int porl_qnet_create(const porl_qnet_cfg* c, porl_qnet** out) {
     h->fslab_stride = ru4(cur);
     h->ws.fslab = ok ? take((int64_t)nblk * h->fslab_stride) : 0;
   }
+  // appended behind everything older, so every earlier offset keeps its meaning
+  h->ws.tmp2[0] = take((int64_t)B * maxld); h->ws.tmp2[1] = take((int64_t)B * maxld);
+  h->ws.row_loss = take(B);
   h->ws.total = o;
   *out = h;
   return PORL_OK;
@@ -2003,8 +2007,10 @@ int porl_qnet_load_batch(porl_qnet* h, int32_t batch, const float* states, int64
 }
 
 // forward of `nnets` parameter sets; set k reads input in_k and writes hidden activations to dst_k[l]
+// tile_as_alone: choose each layer's tile as a launch of one of the (equally shaped) problems alone would, so that every
+// problem of the group runs the tile and K order — hence the bits — of its own single-problem launch
 static int qnet_forward(porl_qnet* h, int nnets, const float* const* params, const float* const* inputs,
-                        float* const (*dst)[PORL_MAX_HIDDEN + 1], int B, hipStream_t s) {
+                        float* const (*dst)[PORL_MAX_HIDDEN + 1], int B, hipStream_t s, bool tile_as_alone = false) {
   const int L = h->cfg.n_hidden;
   for (int l = 0; l <= L; ++l) {
     GemmGroup g{};
@@ -2018,7 +2024,15 @@ static int qnet_forward(porl_qnet* h, int nnets, const float* const* params, con
       p.act = l < L ? ACT_RELU : ACT_NONE;
       g.p[k] = p;
     }
-    PORL_TRY(launch_group(g, pick_tile(g, h->tune), h->tune, s));
+    int tile;
+    if (tile_as_alone) {
+      GemmGroup one{};
+      one.nprob = 1; one.p[0] = g.p[0];
+      tile = pick_tile(one, h->tune);
+    } else {
+      tile = pick_tile(g, h->tune);
+    }
+    PORL_TRY(launch_group(g, tile, h->tune, s));
   }
   return PORL_OK;
 }
@@ -2478,6 +2492,73 @@ int porl_qnet_learn_variant(porl_qnet* h, const float* states, int64_t s_rs, con
     return qnet_general_learn(h, hp, variant, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, idx, (hipStream_t)stream);
   return qnet_fused_backward(h, hp, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, idx,
                              (hipStream_t)stream, true, variant);
+}
+
+// ---- one learn step of the distributional trainers from one call (QR-DQN, C51: dist_losses.hpp) -------------------------
+// The launches of porl_qnet_load_batch + porl_qnet_forward_loaded (x2 / x3) + porl_qr_loss / porl_c51_loss + porl_qnet_backward +
+// porl_qnet_apply + porl_reduce_mean without the copies between them: one gather, the forwards grouped per layer, the loss
+// head reading the padded output rows and writing dL/dz where the backward chain reads it (the head zero-fills columns
+// A*N .. ld-1, as pack_kernel did), the mean into stats[0].  Same kernels on the same numbers: bit-equal results.
+int porl_qnet_dist_learn(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
+                         const float* next_states, int64_t n_rs, const float* dones, const int64_t* idx, int32_t batch,
+                         const porl_qnet_hyper* hp, const porl_dist_head* head, void* stream) {
+  PORL_TRY(qnet_ready(h, false));
+  if (!hp || !head || !states || !actions || !rewards || !next_states || !dones) PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  if (batch < 1 || batch > h->cfg.max_batch) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", batch, h->cfg.max_batch);
+  if (s_rs < h->cfg.state_dim || n_rs < h->cfg.state_dim) PORL_FAIL(PORL_ERR_INVALID, "row stride below state_dim %d", h->cfg.state_dim);
+  if (head->kind != PORL_DIST_QR && head->kind != PORL_DIST_C51) PORL_FAIL(PORL_ERR_INVALID, "unknown head kind %d", head->kind);
+  if (head->n_sub < 1 || head->n_sub > DIST_MAX_N) PORL_FAIL(PORL_ERR_INVALID, "n_sub %d outside [1,%d]", head->n_sub, DIST_MAX_N);
+  if (head->n_actions < 1 || (int64_t)head->n_actions * head->n_sub != h->cfg.n_actions)
+    PORL_FAIL(PORL_ERR_INVALID, "n_actions %d x n_sub %d != the network's %d outputs", head->n_actions, head->n_sub, h->cfg.n_actions);
+  if (head->kind == PORL_DIST_C51) {
+    if (head->n_sub < 2 || !(head->v_max > head->v_min)) PORL_FAIL(PORL_ERR_INVALID, "C51 needs n_sub >= 2 and v_max > v_min");
+    if (!head->support) PORL_FAIL(PORL_ERR_INVALID, "C51 needs the support (null)");
+  }
+  if (hp->step < 1) PORL_FAIL(PORL_ERR_INVALID, "adam step must be >= 1");
+  DevGuard _dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  float* W = h->buf.workspace;
+  const int L = h->cfg.n_hidden, B = batch, A = head->n_actions, N = head->n_sub;
+  const bool qr = head->kind == PORL_DIST_QR;
+  {
+    QnetGatherArgs a{};
+    a.states = states; a.next_states = next_states; a.s_rs = (long)s_rs; a.n_rs = (long)n_rs;
+    a.actions = actions; a.rew = rewards; a.done = dones; a.idx = idx;
+    a.xs = W + h->ws.xs; a.xn = W + h->ws.xn; a.act_out = reinterpret_cast<int64_t*>(W + h->ws.actions);
+    a.rew_out = W + h->ws.rew; a.done_out = W + h->ws.done;
+    a.B = B; a.S = h->cfg.state_dim; a.ld = h->Sp;
+    hipLaunchKernelGGL(qnet_gather_kernel, dim3((unsigned)(((long)B * h->Sp + 255) / 256)), dim3(256), 0, s, a);
+    PORL_HIP(hipGetLastError());
+  }
+  h->batch = B;
+  // online net on s (kept), target net on s', QR-DQN: online net on s' — one launch per layer
+  float* dst[3][PORL_MAX_HIDDEN + 1];
+  for (int l = 0; l <= L; ++l) { dst[0][l] = W + h->ws.act[l]; dst[1][l] = W + h->ws.tmp[l & 1]; dst[2][l] = W + h->ws.tmp2[l & 1]; }
+  const float* params[3] = {h->buf.params, h->buf.params_tgt, h->buf.params};
+  const float* inputs[3] = {W + h->ws.xs, W + h->ws.xn, W + h->ws.xn};
+  PORL_TRY(qnet_forward(h, qr ? 3 : 2, params, inputs, dst, B, s, true));
+  float* dz = W + h->ws.dz[L & 1];
+  float* row_loss = W + h->ws.row_loss;
+  const int64_t* act = reinterpret_cast<const int64_t*>(W + h->ws.actions);
+  if (qr) {
+    QrLossArgs a{dst[0][L], dst[2][L], dst[1][L], (long)h->ld[L], act, W + h->ws.rew, W + h->ws.done, dz, row_loss, B, A, N,
+                 hp->gamma, head->kappa, 1.0f / B};
+    hipLaunchKernelGGL(qr_loss_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, a);
+  } else {
+    const float delta = (float)(((double)head->v_max - (double)head->v_min) / (double)(N - 1));      // as porl_c51_loss
+    C51LossArgs a{dst[0][L], dst[1][L], (long)h->ld[L], act, W + h->ws.rew, W + h->ws.done, head->support, dz, row_loss, B, A, N,
+                  hp->gamma, head->v_min, head->v_max, delta, 1.0f / B};
+    hipLaunchKernelGGL(c51_loss_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, a);
+  }
+  PORL_HIP(hipGetLastError());
+  {
+    ReduceArgs r{};
+    add_reduce(r, h->buf.stats, row_loss, 1, 1, B, 0, 1.0f / B);       // porl_reduce_mean's job
+    PORL_TRY(launch_reduce(r, s));
+  }
+  PORL_TRY(qnet_backward_chain(h, dz, B, s));
+  return adam_launch(h->buf.params, h->buf.grads, h->buf.adam_m, h->buf.adam_v, nullptr, h->n_params, hp->lr, hp->step,
+                     hp->adam_beta1, hp->adam_beta2, hp->adam_eps, 0.0, s);
 }
 
 int porl_qnet_sync_target(porl_qnet* h, void* stream) {

@@ -40,6 +40,12 @@ class C51Trainer(DistTrainerBase):
                                                 N.ptr(self._row_loss), N.current_stream_ptr(self.device)), "porl_c51_loss")
         return self._backward_and_step(dl, B)
 
+    _rows_for = learn_on
+
+    def _dist_head(self):
+        return N.DistHead(1, self.action_size, self.atom_size, 0.0, float(self.v_min), float(self.v_max),
+                          self.support.data_ptr())
+
     def select_action(self, state: np.ndarray) -> int:
         if np.random.rand() < self.epsilon:
             return int(np.random.randint(self.action_size))

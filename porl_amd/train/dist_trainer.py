@@ -6,6 +6,10 @@
 Every arithmetic step is a HIP kernel behind the C ABI (porl_qnet_forward_loaded / porl_qr_loss / porl_c51_loss /
 porl_qnet_backward / porl_qnet_apply / porl_reduce_mean).  The output layer is wider than the one-launch step kernel's
 128 columns (actions x quantiles), so these trainers use the grouped-GEMM path like any wide Q-network.
+
+`learn_indexed(idx)` is the same step on rows `idx` of the replay mirror from ONE native call (porl_qnet_dist_learn:
+gather, the forwards grouped per layer, loss head on the padded rows, mean loss into the engine's statistics, backward,
+Adam) — bit-equal parameters, moments and loss, no copies between the stages; `train_online` learns through it.
 """
 from __future__ import annotations
 
@@ -16,6 +20,7 @@ import torch
 
 from .. import _native as N
 from ..buffer.replay_buffer import ReplayBuffer
+from ..parallel import GradExchange
 from ..utils.logger import Logger
 from .cql_trainer import QnetEngine, _FlatAdam
 
@@ -48,6 +53,7 @@ class DistTrainerBase:
         self.training_learning_step = transition_learning_step     # train_online's learn threshold (dqn_trainer.py:62)
         self.logger = Logger(log_dir=log_dir)
         self.async_losses = False
+        self._exchange = GradExchange()         # train_online keeps the plain loop while a gradient exchange is active
         mb = eng.cfg.max_batch
         self._out = [torch.empty(mb, n_out, dtype=torch.float32, device=self.device) for _ in range(3)]
         self._dout = torch.empty(mb, n_out, dtype=torch.float32, device=self.device)
@@ -88,6 +94,56 @@ class DistTrainerBase:
     def learn(self):
         return self.learn_on(*self.replay_buffer.sample(self.batch_size))
 
+    # -- the same step on rows of the replay mirror, one native call -------------------------------------------------
+    _rows_for = None                   # the subclass's learn_on that _dist_head describes (overriding learn_on opts out)
+
+    def _dist_head(self):
+        """N.DistHead of this trainer's loss (kind, actions, quantiles / atoms, kappa, v_min, v_max, support)."""
+        raise NotImplementedError
+
+    def _learn_rows(self, idx):
+        """Launch learn_on on rows `idx` (device int64) of the replay mirror; the mean loss lands in eng.stats[0]."""
+        eng, m = self._engine, self.replay_buffer._mirror
+        eng._ensure_bound()
+        B = idx.numel()
+        if B < 1 or B > eng.cfg.max_batch:
+            raise RuntimeError(f"batch {B} outside [1, {eng.cfg.max_batch}]")
+        if idx.dtype != torch.int64 or idx.device != eng.device or not idx.is_contiguous():
+            raise RuntimeError(f"idx: need a contiguous int64 tensor on {eng.device}")
+        for k, dt in (("states", torch.float32), ("next_states", torch.float32), ("actions", torch.int64),
+                      ("rewards", torch.float32), ("dones", torch.float32)):
+            if m[k].dtype != dt or m[k].device != eng.device or not m[k].is_contiguous():
+                raise RuntimeError(f"mirror {k}: need a contiguous {dt} tensor on {eng.device}")
+        S = eng.cfg.state_dim
+        if m["states"].shape[1:].numel() != S or m["next_states"].shape != m["states"].shape:
+            raise RuntimeError("replay arrays do not match the network's state_dim")
+        g = self.optimizer.param_groups[0]
+        hp = eng.hyper(self.gamma, 0.0, 1.0 / B, self.optimizer.step_count + 1, g["lr"], g["betas"], g["eps"])
+        head = self._dist_head()
+        N.check(eng._lib.porl_qnet_dist_learn(eng._h, N.ptr(m["states"]), S, N.ptr(m["actions"]), N.ptr(m["rewards"]),
+                                              N.ptr(m["next_states"]), S, N.ptr(m["dones"]), N.ptr(idx), B, C.byref(hp),
+                                              C.byref(head), N.current_stream_ptr(eng.device)), "porl_qnet_dist_learn")
+        self.optimizer.step_count += 1
+
+    def learn_indexed(self, idx):
+        """learn_on(*replay_buffer.sample_at(idx)) from one native call: same parameters, Adam moments and loss, bit for
+        bit.  `idx`: int64 row numbers of the replay buffer (device tensor, or anything numpy converts)."""
+        if self.device.type != "cuda":
+            raise N.NativeError("porl_amd computes on a HIP device only (device='cuda'); there is no CPU path")
+        if not torch.is_tensor(idx):
+            idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(self.device)
+        self.replay_buffer._sync_mirror()
+        self._learn_rows(idx)
+        stats = self._engine.stats
+        if self.async_losses:
+            return stats[:1]
+        loss = float(stats[0])
+        if loss != loss:
+            a = self.replay_buffer._mirror["actions"][idx]
+            if not bool(((a >= 0) & (a < self.action_size)).all()):              # learn_on's rule (_backward_and_step)
+                raise IndexError("action index out of range in the minibatch (valid: 0..%d)" % (self.action_size - 1))
+        return loss
+
     def sync_target(self):
         self._engine.sync_target()
 
@@ -112,12 +168,17 @@ class DistTrainerBase:
 
     def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
         """dqn_trainer.py:119-180 / c51_trainer.py:176-225; greedy actions and pushes take the one-launch forms when the
-        network fits the act kernel, learn() keeps its multi-launch form."""
+        network fits the act kernel, and the learn step runs from one native call on the sampled rows of the mirror
+        (_learn_rows; its loss is read with the next act record) unless a subclass overrides learn / learn_on or a
+        gradient exchange is active — then learn() as it stands."""
         from . import online
         fast = None
-        if online.fast_ok(self) and type(self)._act_for is type(self).select_action:
+        cls = type(self)
+        if online.fast_ok(self) and cls._act_for is cls.select_action:
             kind, n_sub, support = self._act_epilogue()
-            fast = online._Fast(self, kind=kind, n_sub=n_sub, support=support)
+            rows = cls.learn is DistTrainerBase.learn and cls._rows_for is not None and cls._rows_for is cls.learn_on \
+                and not self._exchange.active
+            fast = online._Fast(self, kind=kind, n_sub=n_sub, support=support, learn_rows=self._learn_rows if rows else None)
         threshold = self.batch_size if self._online_threshold == "batch" else self.training_learning_step
         return online.run(self, env, policy, num_episodes, max_steps, threshold, self.replay_buffer,
                           self.replay_buffer.push, fast)

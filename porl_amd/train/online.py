@@ -14,6 +14,10 @@ Fast path (`_Fast`), taken when the network lives on a QnetEngine and the memory
     once: the act record carries the statistics of the step before it, and losses of steps followed by an exploring
     step are parked in a device log, read at the next greedy action or the episode's end.  The logger calls are
     replayed then, in their original order.
+  * learn (C51 / QR-DQN, whose A x N outputs the step kernel does not cover): the same index ring and deferred loss
+    around DistTrainerBase._learn_rows — one native call (porl_qnet_dist_learn) that gathers the rows, runs the
+    forwards as one grouped launch per layer, the loss head on the padded output rows, backward and Adam, and leaves the
+    mean loss in the engine's statistics.
 PER flavour (`_FastPER`, PERTrainer on the one-launch step kernel; dqn_per_trainer.py:127-175): the memory is the
 device-resident PrioritizedReplayBuffer, so
   * push: PrioritizedReplayBuffer.record — one launch writes the row and the leaf (max_initial_priority) and

@@ -40,6 +40,11 @@ class QRDQNTrainer(DistTrainerBase):
                                                N.current_stream_ptr(self.device)), "porl_qr_loss")
         return self._backward_and_step(dz, B)
 
+    _rows_for = learn_on
+
+    def _dist_head(self):
+        return N.DistHead(0, self.action_size, self.num_quantiles, float(self.kappa), 0.0, 0.0, None)
+
     def select_action(self, state: np.ndarray) -> int:
         if np.random.rand() < self.epsilon:
             return int(np.random.randint(self.action_size))
