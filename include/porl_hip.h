@@ -420,6 +420,78 @@ int porl_qnet_act(porl_qnet* h, int which, const porl_qnet_act_src* src, const p
                   int32_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * IQN engine: IQNTrainer.learn (src/porl/train/iqn_trainer.py:92-134) and its greedy action (:82-91) on
+ * IQNNetwork(state, actions, embedding_dim, hidden) (src/porl/net/iqn_network.py:10-62) from one call each.
+ * The engine owns no parameters: it binds to flat buffers that hold the network's ten tensors in
+ * parameters() order — feature_net.0 w/b, feature_net.2 w/b, quantile_embedding w/b, value_net.0 w/b,
+ * value_net.2 w/b — each dense row-major (out, in) at cfg.offset[i] floats (a multiple of 4; gaps are
+ * never written), n_params floats per buffer.  Limits: embedding_dim <= 128, n_actions <= 64, max_tau
+ * (fractions per state) <= 256, else PORL_ERR_UNSUPPORTED.
+ * porl_iqn_learn: rows idx[b] (NULL: rows 0..batch-1) of the replay arrays; taus_prime (batch, n_cur) and
+ *   taus_dprime (batch, n_tgt) dense on the device.  Gather, the three forwards grouped per layer, loss head, mean loss
+ *   -> stats[0], backward into `grads` (every tensor stored whole), clip_grad_norm_(max_norm) with the total norm ->
+ *   stats[1] and the coefficient -> stats[2], Adam.  No host synchronisation.  A row whose action is outside
+ *   0..n_actions-1 contributes no gradient and makes stats[0] NaN.
+ * porl_iqn_act: greedy action of ONE state (src->batch == 1; a row of a device array or inline, <= 256 floats) under
+ *   n_tau fractions `taus` (device): argmax_a mean_n Z(s, tau_n)[a], first maximum.  `record` as porl_qnet_act's:
+ *   int32 action at word 0, fp32 stats[0, n_stats) at words 8.., device or pinned host memory.  which: 0 online, 1 target.
+ * porl_iqn_mix / porl_iqn_head: the two fused kernels of the step on their own (tests).  mix: out[(b, n), :] =
+ *   feat[b, :] * (cos(pi i tau[b, n])_{i=1..E} . weight^T + bias) for 1..3 problems in one launch, emb (optional) = the
+ *   factor in brackets.  head: Double-DQN choice on the tau''-mean of z_online_next, Bellman targets from z_target_next,
+ *   quantile-Huber loss of the taken action's quantiles of z_cur against them; z rows (batch * n, ld); dz (batch * n_cur,
+ *   ld) = dL/dz_cur for the batch-mean loss, row_loss (batch), next_actions (batch, optional).
+ * --------------------------------------------------------------------------------------------- */
+#define PORL_IQN_TENSORS 10
+typedef struct porl_iqn porl_iqn;
+typedef struct porl_iqn_cfg {
+  int32_t state_dim, n_actions, embedding_dim, hidden;
+  int32_t max_batch, max_tau;
+  int64_t offset[PORL_IQN_TENSORS];
+  int64_t n_params;
+} porl_iqn_cfg;
+typedef struct porl_iqn_buffers {
+  float* params;
+  float* params_tgt;
+  float* grads;
+  float* adam_m;
+  float* adam_v;
+  float* workspace;
+  float* stats;               /* >= 8 floats */
+} porl_iqn_buffers;
+typedef struct porl_iqn_hyper {
+  float gamma, kappa, max_norm;
+  int32_t step;               /* Adam step count of this update, >= 1 */
+  double lr, adam_beta1, adam_beta2, adam_eps;
+} porl_iqn_hyper;
+typedef struct porl_iqn_mix_prob {
+  const float* feat;          /* (batch, hidden), row stride ldf */
+  int64_t ldf;
+  const float* taus;          /* (batch * n_tau) */
+  const float* weight;        /* (hidden, embedding_dim), row stride ldw */
+  int64_t ldw;
+  const float* bias;          /* (hidden) */
+  float* out;                 /* (batch * n_tau, hidden), row stride ldo */
+  int64_t ldo;
+  float* emb;                 /* like out, or NULL */
+  int32_t batch, n_tau;
+} porl_iqn_mix_prob;
+int porl_iqn_create(const porl_iqn_cfg* cfg, porl_iqn** out);
+void porl_iqn_destroy(porl_iqn* h);
+int64_t porl_iqn_workspace_floats(const porl_iqn* h);
+int porl_iqn_bind(porl_iqn* h, const porl_iqn_buffers* buffers);
+int porl_iqn_learn(porl_iqn* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
+                   const float* next_states, int64_t n_rs, const float* dones, const int64_t* idx, int32_t batch,
+                   const float* taus_prime, int32_t n_cur, const float* taus_dprime, int32_t n_tgt,
+                   const porl_iqn_hyper* hp, void* stream);
+int porl_iqn_act(porl_iqn* h, int which, const porl_qnet_act_src* src, const float* taus, int32_t n_tau,
+                 int32_t n_stats, int32_t* record, void* stream);
+int porl_iqn_mix(int32_t nprob, const porl_iqn_mix_prob* probs, int32_t embedding_dim, int32_t hidden, void* stream);
+int porl_iqn_head(const float* z_cur, const float* z_online_next, const float* z_target_next, int64_t ld,
+                  const int64_t* actions, const float* rewards, const float* dones, const float* taus_prime,
+                  int32_t batch, int32_t n_cur, int32_t n_tgt, int32_t n_actions, float gamma, float kappa, float* dz,
+                  float* row_loss, int64_t* next_actions, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Building blocks, exported for tests, the replay buffer and other trainers
  * --------------------------------------------------------------------------------------------- */
 /* C = epilogue(op(A) * op(B)); mode 0 "NT": A (M,K), B (N,K); 1 "NN": A (M,K), B (K,N);

@@ -30,6 +30,8 @@ SYMBOLS = [
     "porl_qnet_cql_backward", "porl_qnet_apply", "porl_qnet_learn", "porl_qnet_sync_target",
     "porl_qnet_forward", "porl_qnet_forward_loaded", "porl_qnet_backward", "porl_qr_loss", "porl_iqn_quantile_huber", "porl_iqn_cos_embed", "porl_iqn_hadamard", "porl_iqn_hadamard_backward", "porl_iqn_select", "porl_iqn_scatter", "porl_iqn_target", "porl_grad_clip", "porl_c51_loss", "porl_reduce_mean", "porl_qnet_penalty", "porl_qnet_learn_indexed", "porl_qnet_one_launch", "porl_qnet_learn_variant", "porl_qnet_can_sample", "porl_qnet_learn_sampled", "porl_qnet_dist_learn",
     "porl_qnet_record", "porl_qnet_act_ok", "porl_qnet_act",
+    "porl_iqn_create", "porl_iqn_destroy", "porl_iqn_workspace_floats", "porl_iqn_bind", "porl_iqn_learn", "porl_iqn_act",
+    "porl_iqn_mix", "porl_iqn_head",
     "porl_enc_create", "porl_enc_destroy", "porl_enc_param_floats", "porl_enc_stat_floats",
     "porl_enc_workspace_floats", "porl_enc_tensors", "porl_enc_norms", "porl_enc_blocks",
     "porl_enc_tensor_info", "porl_enc_norm_info", "porl_enc_bind", "porl_enc_weights_changed", "porl_enc_forward",
@@ -93,6 +95,22 @@ class QnetActSrc(C.Structure):
 class QnetActEpilogue(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_act", C.c_int32), ("n_sub", C.c_int32), ("support", C.c_void_p),
                 ("stats", C.c_void_p), ("n_stats", C.c_int32)]
+
+
+class IqnCfg(C.Structure):
+    _fields_ = [("state_dim", C.c_int32), ("n_actions", C.c_int32), ("embedding_dim", C.c_int32), ("hidden", C.c_int32),
+                ("max_batch", C.c_int32), ("max_tau", C.c_int32), ("offset", C.c_int64 * 10), ("n_params", C.c_int64)]
+
+
+class IqnHyper(C.Structure):
+    _fields_ = [("gamma", C.c_float), ("kappa", C.c_float), ("max_norm", C.c_float), ("step", C.c_int32),
+                ("lr", C.c_double), ("adam_beta1", C.c_double), ("adam_beta2", C.c_double), ("adam_eps", C.c_double)]
+
+
+class IqnMixProb(C.Structure):
+    _fields_ = [("feat", C.c_void_p), ("ldf", C.c_int64), ("taus", C.c_void_p), ("weight", C.c_void_p), ("ldw", C.c_int64),
+                ("bias", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64), ("emb", C.c_void_p), ("batch", C.c_int32),
+                ("n_tau", C.c_int32)]
 
 
 class EncCfg(C.Structure):
@@ -206,6 +224,16 @@ def _declare(lib):
     lib.porl_qnet_act_ok.argtypes = [vp]
     lib.porl_qnet_act_ok.restype = i32
     lib.porl_qnet_act.argtypes = [vp, C.c_int, C.POINTER(QnetActSrc), C.POINTER(QnetActEpilogue), vp, vp]
+    lib.porl_iqn_create.argtypes = [C.POINTER(IqnCfg), C.POINTER(vp)]
+    lib.porl_iqn_destroy.argtypes = [vp]
+    lib.porl_iqn_destroy.restype = None
+    lib.porl_iqn_workspace_floats.argtypes = [vp]
+    lib.porl_iqn_workspace_floats.restype = i64
+    lib.porl_iqn_bind.argtypes = [vp, C.POINTER(QnetBuffers)]           # porl_iqn_buffers has porl_qnet_buffers' fields
+    lib.porl_iqn_learn.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, vp, i32, vp, i32, C.POINTER(IqnHyper), vp]
+    lib.porl_iqn_act.argtypes = [vp, C.c_int, C.POINTER(QnetActSrc), vp, i32, i32, vp, vp]
+    lib.porl_iqn_mix.argtypes = [i32, C.POINTER(IqnMixProb), i32, i32, vp]
+    lib.porl_iqn_head.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp]
     lib.porl_enc_create.argtypes = [C.POINTER(EncCfg), C.POINTER(vp)]
     lib.porl_enc_destroy.argtypes = [vp]
     lib.porl_enc_destroy.restype = None

@@ -2721,3 +2721,4 @@ int porl_qnet_act(porl_qnet* h, int which, const porl_qnet_act_src* src, const p
 }  // extern "C"
 
 #include "encoder_api.inc"
+#include "iqn_api.inc"

@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -358,6 +359,96 @@ class IqlEngine:
             self._free_signals()
             if getattr(self, "_h", None):
                 self._lib.porl_iql_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class IqnEngine:
+    """The IQN engine of the C ABI (porl_iqn_*): one learn step / one greedy action of IQNTrainer per native call, on flat
+    buffers the caller owns (`bind`).  Tensors in IQNNetwork.parameters() order, each starting on a 16-byte boundary —
+    the layout train.iqn_trainer._FlatAdam builds."""
+
+    MAX_EMBED, MAX_TAU, MAX_ACTIONS, ACT_MAX_INLINE = 128, 256, 64, 256
+
+    def __init__(self, state_dim, n_actions, embedding_dim, hidden, max_batch, max_tau, device):
+        self.device = _norm_device(device)
+        S, A, Ed, H = int(state_dim), int(n_actions), int(embedding_dim), int(hidden)
+        numel = [H * S, H, H * H, H, H * Ed, H, H * H, H, A * H, A]
+        offs, off = [], 0
+        for k in numel:
+            offs.append(off)
+            off += (k + 3) // 4 * 4
+        self.offsets, self.n_params = offs, off
+        self.cfg = N.IqnCfg(S, A, Ed, H, int(max_batch), int(max_tau), (C.c_int64 * 10)(*offs), off)
+        self._lib = N.lib()
+        h = C.c_void_p()
+        N.check(self._lib.porl_iqn_create(C.byref(self.cfg), C.byref(h)), "porl_iqn_create")
+        self._h = h
+        self.stats = self.workspace = None
+        self._bound = False
+
+    def bind(self, params, params_tgt, grads, adam_m, adam_v):
+        if self.device.type != "cuda":
+            raise N.NativeError("porl_amd computes on a HIP device only (device='cuda'); there is no CPU path")
+        for name, t in (("params", params), ("params_tgt", params_tgt), ("grads", grads), ("adam_m", adam_m), ("adam_v", adam_v)):
+            if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or t.numel() != self.n_params:
+                raise RuntimeError(f"{name}: need {self.n_params} contiguous float32 on {self.device}")
+        self.workspace = torch.empty(int(self._lib.porl_iqn_workspace_floats(self._h)), dtype=torch.float32, device=self.device)
+        self.stats = torch.zeros(8, dtype=torch.float32, device=self.device)
+        self._held = (params, params_tgt, grads, adam_m, adam_v)
+        b = N.QnetBuffers(*[C.c_void_p(t.data_ptr()) for t in (*self._held, self.workspace, self.stats)])
+        N.check(self._lib.porl_iqn_bind(self._h, C.byref(b)), "porl_iqn_bind")
+        self._bound = True
+        return self
+
+    def hyper(self, gamma, kappa, max_norm, step, lr, betas=(0.9, 0.999), eps=1e-8):
+        return N.IqnHyper(gamma, kappa, max_norm, step, lr, betas[0], betas[1], eps)
+
+    def learn(self, hp, states, actions, rewards, next_states, dones, idx, taus_prime, taus_double_prime):
+        """One learn step on rows `idx` (int64, device) of the replay arrays (porl_iqn_learn); the mean loss, the total
+        gradient norm and the clip coefficient land in stats[0:3]."""
+        B = idx.numel()
+        for name, x, dt in (("states", states, torch.float32), ("next_states", next_states, torch.float32),
+                            ("actions", actions, torch.int64), ("rewards", rewards, torch.float32),
+                            ("dones", dones, torch.float32), ("idx", idx, torch.int64),
+                            ("taus_prime", taus_prime, torch.float32), ("taus_double_prime", taus_double_prime, torch.float32)):
+            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
+                raise RuntimeError(f"{name}: need a contiguous {dt} tensor on {self.device}")
+        S = self.cfg.state_dim
+        if states.shape[1:].numel() != S or next_states.shape != states.shape:
+            raise RuntimeError("replay arrays do not match the network's state_dim")
+        if taus_prime.dim() != 2 or taus_double_prime.dim() != 2 or taus_prime.shape[0] != B or taus_double_prime.shape[0] != B:
+            raise RuntimeError("fractions: expected (batch, n) tensors")
+        N.check(self._lib.porl_iqn_learn(self._h, N.ptr(states), S, N.ptr(actions), N.ptr(rewards), N.ptr(next_states), S,
+                                         N.ptr(dones), N.ptr(idx), B, N.ptr(taus_prime), taus_prime.shape[1],
+                                         N.ptr(taus_double_prime), taus_double_prime.shape[1], C.byref(hp),
+                                         N.current_stream_ptr(self.device)), "porl_iqn_learn")
+        return B
+
+    def act(self, out, taus, states=None, row=0, inline=None, which=0, n_stats=0):
+        """Greedy action of one state in the int32 record `out` (16 words, device or pinned host; porl_iqn_act):
+        out[0] = argmax_a mean_n Z(s, taus[n])[a] for row `row` of the device array `states` or the host floats `inline`;
+        out[8:8+n_stats] (as fp32) = the engine's statistics in stream order."""
+        if taus.dtype != torch.float32 or taus.device != self.device or not taus.is_contiguous():
+            raise RuntimeError(f"taus: need contiguous float32 on {self.device}")
+        if states is not None:
+            if states.dtype != torch.float32 or states.device != self.device or states.stride(-1) != 1:
+                raise RuntimeError(f"states: need float32 rows on {self.device}")
+            src = N.QnetActSrc(1, states.data_ptr(), states.stride(0), int(row), states.shape[0], None)
+        else:
+            inline = np.ascontiguousarray(inline, dtype=np.float32).reshape(-1)
+            if inline.size != self.cfg.state_dim:
+                raise RuntimeError(f"state: expected {self.cfg.state_dim} floats, got {inline.size}")
+            src = N.QnetActSrc(1, None, self.cfg.state_dim, 0, 0, inline.ctypes.data)
+        N.check(self._lib.porl_iqn_act(self._h, int(which), C.byref(src), N.ptr(taus), taus.numel(), int(n_stats),
+                                       C.c_void_p(out.data_ptr()), N.current_stream_ptr(self.device)), "porl_iqn_act")
+        return out
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.porl_iqn_destroy(self._h)
                 self._h = None
         except Exception:
             pass

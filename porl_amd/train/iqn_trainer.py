@@ -18,6 +18,11 @@ bypassed, `get_q_values` bound to the live network's forward) on fixed minibatch
 
 Arithmetic: Linear layers on the fp32-MFMA GEMM, the rest on csrc/iqn.hpp and dist_losses.hpp (iqn_loss_kernel);
 parameters, gradients and Adam moments live in one flat buffer each (clip and Adam are single sweeps).  No CPU path.
+
+`learn_indexed` / `act_greedy` are the same step and the same greedy action from ONE native call each (engine.IqnEngine,
+csrc/iqn_api.inc) on rows of the replay mirror: no autograd, no intermediate torch tensor, no host synchronisation inside
+the step.  The engine binds to the flat buffers above, so both paths share one state and may be interleaved.
+`train_online` runs on them (train/online.py:_FastIQN) when nothing the loop calls has been overridden.
 """
 from __future__ import annotations
 
@@ -121,6 +126,8 @@ class IQNTrainer:
         self.logger = Logger(log_dir=log_dir)
         self.async_losses = False
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._iqn = None                       # engine.IqnEngine, made on first use (learn_indexed / act_greedy)
+        self._taus = {}                        # preallocated fraction buffers by use and shape
 
     def sync_target(self):
         self._target.flat.copy_(self.optimizer.flat)
@@ -181,6 +188,102 @@ class IQNTrainer:
             raise IndexError("action index out of range in the minibatch (valid: 0..%d)" % (A - 1))    # upstream's gather raises
         return loss
 
+    # -- the same step / action from one native call (csrc/iqn_api.inc) ------------------------------------------------
+    def _views_intact(self):
+        """The networks' parameters still are the views into the flat buffers that _FlatAdam made, in its layout."""
+        ru4 = lambda k: (k + 3) // 4 * 4
+        for net, flat in ((self.q_network, self.optimizer), (self.target_network, self._target)):
+            off = 0
+            for p in net.parameters():
+                if p.data_ptr() != flat.flat.data_ptr() + 4 * off or not p.is_contiguous():
+                    return False
+                off += ru4(p.numel())
+        return True
+
+    def _native_engine(self, batch=0, n_tau=0):
+        q = self.q_network
+        H = q.feature_net[0].out_features
+        need_b = max(batch, self.batch_size)
+        need_t = max(n_tau, self.num_quantiles_n_policy, self.num_quantiles_n_prime_loss,
+                     self.num_quantiles_n_double_prime_loss)
+        eng = self._iqn
+        if eng is None or eng.cfg.max_batch < need_b or eng.cfg.max_tau < need_t:
+            if type(q) is not IQNNetwork or type(self.target_network) is not IQNNetwork or not self._views_intact():
+                raise RuntimeError("the native IQN step needs both networks to be IQNNetwork on the trainer's flat buffers")
+            eng = E.IqnEngine(self.state_size, self.action_size, self.embedding_dim, H, need_b, need_t, self.device)
+            o = self.optimizer
+            if eng.n_params != o.flat.numel():
+                raise RuntimeError("flat parameter layout does not match the engine's")
+            eng.bind(o.flat, self._target.flat, o.grad, o.exp_avg, o.exp_avg_sq)
+            self._iqn = eng
+        return eng
+
+    def _rand(self, which, rows, n):
+        """torch.rand(rows, n, device=...) into a buffer kept per use and shape: the draw learn() / select_action make."""
+        buf = self._taus.get((which, rows, n))
+        if buf is None:
+            buf = self._taus[(which, rows, n)] = torch.empty(rows, n, dtype=torch.float32, device=self.device)
+        return torch.rand((rows, n), out=buf)
+
+    def _learn_rows(self, idx, taus_prime=None, taus_double_prime=None):
+        """learn() on rows `idx` of the replay mirror, launched and not waited for; the statistics are in _iqn.stats."""
+        B = idx.numel()
+        if taus_prime is None:                                   # learn()'s draws, in its order
+            taus_prime = self._rand("prime", B, self.num_quantiles_n_prime_loss)
+        if taus_double_prime is None:
+            taus_double_prime = self._rand("double_prime", B, self.num_quantiles_n_double_prime_loss)
+        tp = taus_prime.to(self.device).float().contiguous()
+        tpp = taus_double_prime.to(self.device).float().contiguous()
+        eng = self._native_engine(B, max(tp.shape[1], tpp.shape[1]))
+        rb = self.replay_buffer
+        rb._sync_mirror()
+        m = rb._mirror
+        o = self.optimizer
+        o.step_count += 1
+        g = o.param_groups[0]
+        hp = eng.hyper(self.gamma, self.kappa, self.max_norm, o.step_count, g["lr"], g["betas"], g["eps"])
+        eng.learn(hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"], idx, tp, tpp)
+        return eng
+
+    def learn_indexed(self, idx, taus_prime=None, taus_double_prime=None):
+        """learn_on() on rows `idx` (device int64) of the replay buffer's device mirror, from one native call.  Fractions
+        not given are drawn as learn() draws them (tau' first, then tau'').  Returns the loss as a float — raising
+        learn_on's IndexError for an action outside 0..A-1 — or, with async_losses, the device statistics (loss, total
+        gradient norm, clip coefficient)."""
+        eng = self._learn_rows(idx, taus_prime, taus_double_prime)
+        if self.async_losses:
+            return eng.stats[:3]
+        loss = float(eng.stats[0])
+        if loss != loss:
+            a = self.replay_buffer._mirror["actions"][idx]
+            if not bool(((a >= 0) & (a < self.action_size)).all()):
+                raise IndexError("action index out of range in the minibatch (valid: 0..%d)" % (self.action_size - 1))
+        return loss
+
+    def _act(self, rec, state=None, row=None, taus=None, n_stats=0, array="states"):
+        """Launch the greedy action into the record `rec` (not waited for): `state` inline, or row `row` of the replay
+        mirror's `array`."""
+        if taus is None:                                         # select_action's draw
+            taus = self._rand("policy", 1, self.num_quantiles_n_policy)
+        taus = taus.to(self.device).float().contiguous()
+        eng = self._native_engine(0, taus.numel())
+        if row is not None:
+            self.replay_buffer._sync_mirror()
+            eng.act(rec, taus, states=self.replay_buffer._mirror[array], row=row, n_stats=n_stats)
+        else:
+            eng.act(rec, taus, inline=state, n_stats=n_stats)
+
+    def act_greedy(self, state=None, row=None, taus=None) -> int:
+        """select_action's greedy branch from one native call (porl_iqn_act): `state` (host floats), or row `row` of the
+        replay mirror's states; fractions (1, N) drawn as select_action draws them unless given."""
+        if (state is None) == (row is None):
+            raise ValueError("give either a state or a row of the replay mirror")
+        if getattr(self, "_rec", None) is None:
+            self._rec = torch.zeros(16, dtype=torch.int32).pin_memory()
+        self._act(self._rec, state=state, row=row, taus=taus)
+        torch.cuda.current_stream(self.device).synchronize()
+        return int(self._rec[0])
+
     def train_offline(self, policy=None, num_iterations: int = 10000):
         """dqn_trainer.py:182-204 (inherited by the reference's IQNTrainer)."""
         losses = []
@@ -197,5 +300,6 @@ class IQNTrainer:
         """dqn_trainer.py:119-180 (inherited by the reference's IQNTrainer) on this trainer's select_action (it samples
         its own quantile fractions), push and learn; learns once len(replay_buffer) >= training_learning_step."""
         from . import online
+        fast = online._FastIQN(self) if online.fast_iqn_ok(self) else None
         return online.run(self, env, policy, num_episodes, max_steps, self.training_learning_step, self.replay_buffer,
-                          self.replay_buffer.push)
+                          self.replay_buffer.push, fast=fast)

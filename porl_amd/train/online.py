@@ -25,8 +25,16 @@ device-resident PrioritizedReplayBuffer, so
   * learn: sample_slots (one copy of the batch's uniforms, drawn from Python's `random` exactly as the reference draws
     them, one launch for tree walk, weights and their mean) -> the step kernel on rows `slots` (Double-DQN, importance
     weights or their mean, |TD| out) -> update_priorities_device (one launch); losses deferred as above.
-Everything else (IQN, user `policy` callables, networks too large for one workgroup) runs the reference loop on the
-trainer's own select_action / push / learn.
+IQN flavour (`_FastIQN`, IQNTrainer; the reference's scripts/train_iqn.py drives exactly this loop): the network is not
+an MLP a QnetEngine covers, so the trainer's own IqnEngine (csrc/iqn_api.inc) stands in for it:
+  * greedy action: the fractions are drawn as select_action draws them (torch.rand(1, N_policy) on the device), then
+    porl_iqn_act — feature net on the one state, mix kernel, value layer, act head — writes the same pinned record;
+  * push: ReplayBuffer.record, as above;
+  * learn: the index ring and deferred loss around IQNTrainer._learn_rows — tau' and tau'' drawn as learn() draws them,
+    then one native call (porl_iqn_learn): gather, the three forwards grouped per layer, loss head, backward into the
+    flat gradient buffer, clip, Adam; mean loss, gradient norm and clip coefficient in the engine's statistics.
+Everything else (user `policy` callables, subclasses that override learn / learn_on / select_action, networks too large
+for one workgroup) runs the reference loop on the trainer's own select_action / push / learn.
 """
 from __future__ import annotations
 
@@ -37,8 +45,9 @@ from .. import _native as N
 
 
 class _Fast:
-    def __init__(self, trainer, kind=0, n_sub=1, support=None, learn_rows=None, memory=None):
-        self.t, self.eng, self.rb = trainer, trainer._engine, trainer.replay_buffer if memory is None else memory
+    def __init__(self, trainer, kind=0, n_sub=1, support=None, learn_rows=None, memory=None, engine=None):
+        self.t, self.eng = trainer, trainer._engine if engine is None else engine
+        self.rb = trainer.replay_buffer if memory is None else memory
         self.kind, self.n_sub, self.support = kind, n_sub, support
         self.n_act = trainer.action_size
         self.learn_rows = learn_rows               # None: the trainer's own learn()
@@ -184,6 +193,30 @@ class _FastPER(_Fast):
         return self._deferred_loss()
 
 
+class _FastIQN(_Fast):
+    """IQNTrainer: act and learn on the trainer's IqnEngine; ring, record and deferred losses as _Fast."""
+
+    def __init__(self, trainer):
+        super().__init__(trainer, learn_rows=trainer._learn_rows, engine=trainer._native_engine())
+
+    def greedy(self, state):
+        n_stats = 1 if self.in_stats is not None else 0
+        self.t._act(self.rec, state=state if self.state_row is None else None, row=self.state_row, n_stats=n_stats,
+                    array="next_states")
+        self.stream.synchronize()
+        if n_stats:
+            self.resolve(float(self.rec_f[8]))
+        return int(self.rec[0])
+
+    def push(self, state, action, reward, next_state, done):
+        p = self.rb.position
+        self.state_row = p if self.rb.record(state, action, reward, next_state, done) else None
+
+    def learn(self):
+        self.eng = self.t._native_engine()         # (the same engine unless a larger one had to be made)
+        return super().learn()
+
+
 class _Loss:
     __slots__ = ("i",)
 
@@ -281,3 +314,32 @@ def fast_ok(trainer):
         return False
     eng._ensure_bound()
     return eng.act_ok
+
+
+def fast_iqn_ok(trainer):
+    """The native IQN path applies: a HIP device, the device-mirrored ReplayBuffer with rows that fit the record and
+    inline limits, both networks exactly IQNNetwork on the trainer's flat buffers, learn / learn_on / select_action not
+    overridden, sizes within the engine's limits."""
+    from ..buffer.replay_buffer import ReplayBuffer
+    from ..engine import IqnEngine, _norm_device
+    from ..net.iqn_network import IQNNetwork
+    from ..train.cql_trainer import QnetEngine
+    from .iqn_trainer import IQNTrainer
+    t, rb = trainer, trainer.replay_buffer
+    dev = _norm_device(t.device)
+    if dev.type != "cuda" or type(rb) is not ReplayBuffer or _norm_device(rb.device) != dev:
+        return False
+    if type(t.q_network) is not IQNNetwork or type(t.target_network) is not IQNNetwork:
+        return False
+    cls = type(t)
+    if cls.learn is not IQNTrainer.learn or cls.learn_on is not IQNTrainer.learn_on or \
+            cls.select_action is not IQNTrainer.select_action:
+        return False
+    S = int(np.prod(rb.state_shape))
+    if S != t.state_size or S > QnetEngine.RECORD_MAX_STATE or S > IqnEngine.ACT_MAX_INLINE:
+        return False
+    q = t.q_network
+    if q.embedding_dim != t.embedding_dim or q.embedding_dim > IqnEngine.MAX_EMBED or t.action_size > IqnEngine.MAX_ACTIONS or \
+            max(t.num_quantiles_n_policy, t.num_quantiles_n_prime_loss, t.num_quantiles_n_double_prime_loss) > IqnEngine.MAX_TAU:
+        return False
+    return t._views_intact()

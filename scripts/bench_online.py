@@ -6,7 +6,7 @@ with 1 000 transitions so that every timed step learns.  Two action regimes, rep
   greedy  : epsilon = 0 — every step acts through the network
   explore : epsilon = 1 — every step draws a random action (no forward at all)
 
-    python scripts/bench_online.py [--steps 3000] [--warmup 300] [--trainer dqn|per|c51|qr] [--regime greedy|explore]
+    python scripts/bench_online.py [--steps 3000] [--warmup 300] [--trainer dqn|per|c51|qr|iqn] [--regime greedy|explore]
                                    [--no-reference-loop]
 
 --trainer per: PERTrainer.train_online (Double DQN on prioritized replay, learns from len(memory) >= batch_size on):
@@ -19,6 +19,12 @@ quantiles), same batch and pre-fill, every step learns: the one-launch act / rec
 (porl_qnet_dist_learn on the sampled rows of the mirror) against the loop on select_action + push + learn.  On a tree
 without the one-call learn step the first column times act / record around the multi-launch learn() ("one_launch":
 false) — the figure to compare another tree's against.
+
+--trainer iqn: IQNTrainer.train_online on the class-default network (hidden 512, 64 cosine features, 8 / 8 / 32
+fractions), same batch and pre-fill, every step learns: the native act (porl_iqn_act) / record with the one-call learn
+step (porl_iqn_learn on the sampled rows of the mirror) against the loop on select_action + push + learn.  On a tree
+without the native path both columns time the plain loop ("one_launch": false) — the figure to compare another tree's
+against.
 
 Prints one JSON line.
 """
@@ -168,11 +174,41 @@ def run_dist(kind, fast, eps, steps, warmup):
     return steps / dt, one_launch
 
 
+def run_iqn(fast, eps, steps, warmup):
+    from porl_amd.train.iqn_trainer import IQNTrainer
+    torch.manual_seed(0)
+    np.random.seed(0)
+    t = IQNTrainer(S, A, 0.99, epsilon=eps, epsilon_min=eps, epsilon_decay=1.0, update_target_freq=10, device="cuda",
+                   batch_size=B, buffer_size=CAP, transition_learning_step=B)
+    t.logger = NullLogger()
+    rng = np.random.default_rng(1)
+    for _ in range(PREFILL):
+        t.replay_buffer.push(rng.standard_normal(S).astype(np.float32), int(rng.integers(A)), float(rng.standard_normal()),
+                             rng.standard_normal(S).astype(np.float32), False)
+    t.replay_buffer._sync_mirror()
+    orig = getattr(online, "fast_iqn_ok", None)
+    one_launch = bool(orig is not None and orig(t))
+    if not fast and orig is not None:
+        online.fast_iqn_ok = lambda trainer: False
+    try:
+        with contextlib.redirect_stdout(io.StringIO()):
+            t.train_online(ZeroEnv(warmup), num_episodes=1, max_steps=warmup)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            t.train_online(ZeroEnv(steps), num_episodes=1, max_steps=steps)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+    finally:
+        if orig is not None:
+            online.fast_iqn_ok = orig
+    return steps / dt, one_launch
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=3000)
     ap.add_argument("--warmup", type=int, default=300)
-    ap.add_argument("--trainer", choices=("dqn", "per", "c51", "qr"), default="dqn")
+    ap.add_argument("--trainer", choices=("dqn", "per", "c51", "qr", "iqn"), default="dqn")
     ap.add_argument("--regime", choices=("greedy", "explore", "both"), default="both")
     ap.add_argument("--no-reference-loop", action="store_true", help="time the default path only")
     a = ap.parse_args()
@@ -180,12 +216,17 @@ def main():
     out = {"metric": "train_online env steps/s", "trainer": a.trainer,
            "config": dict(S=S, A=A, hidden=[128, 128] if dist else [64, 128, 64], batch=B, capacity=CAP, steps=a.steps,
                           every_step_learns=True)}
+    if a.trainer == "iqn":
+        out["config"].update(hidden=512, embedding_dim=64, fractions=[8, 8, 32])
     for name, eps in (("greedy", 0.0), ("explore", 1.0)):
         if a.regime not in (name, "both"):
             continue
         if a.trainer == "per":
             fast, out["one_launch"] = run_per(True, eps, a.steps, a.warmup)
             plain = None if a.no_reference_loop else run_per(False, eps, a.steps, a.warmup)[0]
+        elif a.trainer == "iqn":
+            fast, out["one_launch"] = run_iqn(True, eps, a.steps, a.warmup)
+            plain = None if a.no_reference_loop else run_iqn(False, eps, a.steps, a.warmup)[0]
         elif dist:
             fast, out["one_launch"] = run_dist(a.trainer, True, eps, a.steps, a.warmup)
             plain = None if a.no_reference_loop else run_dist(a.trainer, False, eps, a.steps, a.warmup)[0]
