@@ -503,6 +503,54 @@ int porl_gemm_f32(int mode, int tile, int32_t M, int32_t N, int32_t K,
                   const float* bias, int act, const float* mask, int32_t ldmask,
                   int splitk, float* slab, void* stream);
 
+/* One launch of 1..8 independent products on the same kernel, each with the full prologue / epilogue set the engines
+ * use (csrc/gemm_f32.hpp, GemmProb).  A descriptor-level test surface: what a descriptor asks for is what one block
+ * grid computes, nothing is combined afterwards.  Per problem, in this order:
+ *   a(m,k)  = A, or max(A*a_colscale[k] + a_colshift[k], 0) when both are set (NT only, tiles 1, 3, 4, K % 32 == 0),
+ *             or for a_grp > 0 (NT only) the gathered-patch operand: row m starts at m*lda + (m / a_grp)*a_grp_jump
+ *             floats and columns from a_seg_tiles*32 on lie a_seg_jump floats further;
+ *   v       = act(a.b + bias), then v = mask > 0 ? v : 0, then v = resid + rscale[(m + rs_row0) / rs_rows] * v
+ *             (rscale NULL = 1; resid has C's leading dimension and may be C); v is the STORED C (store_c = 0: C is
+ *             not written, the other outputs are);
+ *   cstat   ((M+31)/32, 2, N): per 32-row block the column sums [rb][0][n] and sums of squares [rb][1][n] of the stored C;
+ *   headout (ceil(N/32), M): headout[p][m] = sum of C(m,n)*headw[n] over the 32 columns of part p, from the stored C;
+ *   colsum  (M,): TN only, sum_k A(k,m).
+ * The kernel applies mask / resid after it has taken cstat / the head on some tiles, so a descriptor with (mask or
+ * resid) and (cstat or headw) is refused (PORL_ERR_UNSUPPORTED) rather than computed two ways.
+ * splitk > 1: C and colsum are RAW slab bases (slab s at C + s*M*ldc and colsum + s*M, s < splitk; a slab whose K
+ * range is empty is written with zeros); bias, act, mask, head, resid and cstat are refused with it.
+ * Leading dimensions below the contiguous extent (ldc < N, ldmask < N, lda / ldb below K, M or N by layout), negative
+ * jumps of a gathered A, jumps that are no multiple of 4 floats under a 16-byte-readable A, jumps set for a dense A and
+ * a non-zero `reserved` are refused as well (PORL_ERR_INVALID).
+ * tile as for porl_gemm_f32 (-1 = automatic, 0..4).  single_buffer != 0 asks for the single-LDS-buffer schedule, which exists
+ * on tile 3 with 16-byte-readable operands (elsewhere the usual schedule runs).  Every refusal happens on the host,
+ * before anything is launched. */
+typedef struct porl_gemm_desc {
+  const float* A;
+  const float* B;
+  float* C;
+  const float* bias;
+  const float* mask;
+  const float* headw;
+  float* headout;
+  float* colsum;
+  const float* a_colscale;
+  const float* a_colshift;
+  const float* resid;
+  const float* rscale;
+  float* cstat;
+  int32_t mode;        /* 0 NT, 1 NN, 2 TN */
+  int32_t M, N, K;
+  int32_t lda, ldb, ldc, ldmask;
+  int32_t act;
+  int32_t rs_rows, rs_row0;
+  int32_t a_grp, a_grp_jump, a_seg_tiles, a_seg_jump;
+  int32_t splitk;      /* <= 1: one pass over K */
+  int32_t store_c;
+  int32_t reserved;    /* 0 */
+} porl_gemm_desc;
+int porl_gemm_f32_group(const porl_gemm_desc* probs, int32_t nprob, int tile, int single_buffer, void* stream);
+
 /* torch.optim.Adam single-tensor arithmetic over a flat range (n multiple of 4, 16-byte aligned),
  * optionally fused with target <- (1-ema_beta) target + ema_beta p (target may be NULL). */
 int porl_adam_ema(float* p, const float* g, float* m, float* v, float* target, int64_t n,

@@ -21,7 +21,7 @@ SYMBOLS = [
     "porl_iql_load_batch_sampled", "porl_iql_set_stats", "porl_iql_set_mode", "porl_iql_tune_set",
     "porl_iql_value_backward", "porl_iql_value_apply", "porl_iql_policy_forward", "porl_iql_policy_backward",
     "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_only_forward", "porl_iql_policy_only_step", "porl_iql_policy_prefetch", "porl_iql_forward_value", "porl_iql_forward_policy",
-    "porl_gemm_f32", "porl_adam_ema", "porl_ema", "porl_softmax_mask", "porl_gather_rows", "porl_sample_indices", "porl_epoch_indices", "porl_per_update", "porl_per_sample",
+    "porl_gemm_f32", "porl_gemm_f32_group", "porl_adam_ema", "porl_ema", "porl_softmax_mask", "porl_gather_rows", "porl_sample_indices", "porl_epoch_indices", "porl_per_update", "porl_per_sample",
     "porl_per_record", "porl_per_sample_slots", "porl_per_update_f32",
     "porl_prof_enable", "porl_prof_read", "porl_tune_set", "porl_tune_set_ptr", "porl_state2costmap",
     "porl_signal_create", "porl_signal_destroy", "porl_signal_write", "porl_signal_wait_ge", "porl_iql_update_pipelined",
@@ -113,6 +113,13 @@ class IqnMixProb(C.Structure):
                 ("n_tau", C.c_int32)]
 
 
+class GemmDesc(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("A", "B", "C", "bias", "mask", "headw", "headout", "colsum", "a_colscale",
+                                          "a_colshift", "resid", "rscale", "cstat")] + \
+               [(n, C.c_int32) for n in ("mode", "M", "N", "K", "lda", "ldb", "ldc", "ldmask", "act", "rs_rows", "rs_row0",
+                                         "a_grp", "a_grp_jump", "a_seg_tiles", "a_seg_jump", "splitk", "store_c", "reserved")]
+
+
 class EncCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_ang", "n_dist", "embed_dim", "depth0", "depth1", "n_div",
                                          "feature_dim", "num_classes", "max_batch")] + \
@@ -158,6 +165,7 @@ def _declare(lib):
     lib.porl_iql_forward_policy.argtypes = [vp, vp, i64, i32, vp, i64, vp]
     lib.porl_gemm_f32.argtypes = [C.c_int, C.c_int, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, C.c_int,
                                   vp, i32, C.c_int, vp, vp]
+    lib.porl_gemm_f32_group.argtypes = [C.POINTER(GemmDesc), i32, C.c_int, C.c_int, vp]
     lib.porl_adam_ema.argtypes = [vp, vp, vp, vp, vp, i64, f64, i32, f64, f64, f64, f64, vp]
     lib.porl_ema.argtypes = [vp, vp, i64, f64, vp]
     lib.porl_softmax_mask.argtypes = [vp, i64, i32, i32, f32, i32, vp, vp]

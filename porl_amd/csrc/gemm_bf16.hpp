@@ -197,8 +197,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const GemmGroup g) {
         }
         cs += __shfl_xor(cs, 32);
         cq += __shfl_xor(cq, 32);
-        if (kh == 0 && col_ok) {
-          float* o = P.cstat + (size_t)((m0 + wm * (BM / WM)) / 32 + i) * 2 * N + col;
+        // (as in gemm_f32.hpp: a 32-row block that starts at or past M belongs to no row and is not written)
+        const int rblk = (m0 + wm * (BM / WM)) / 32 + i;
+        if (kh == 0 && col_ok && rblk * 32 < M) {
+          float* o = P.cstat + (size_t)rblk * 2 * N + col;
           o[0] = cs;
           o[N] = cq;
         }

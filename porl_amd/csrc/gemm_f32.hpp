@@ -57,6 +57,7 @@ struct GemmProb {
   const float* resid;     // (M,N) ld=ldc: C = resid + rscale[(row + rs_row0) / rs_rows] * acc (may alias C), or null
   const float* rscale;    // per-sample factor of the residual form (null = 1)
   float* cstat;           // ((M+31)/32, 2, N): per 32-row block, column sums and sums of squares of the stored C
+                          // (cstat / headw are refused together with mask / resid: launch_tile)
   int rs_rows, rs_row0;
   // k-contiguous A whose rows are gathered 2x2 patches of an NHWC tensor (PatchMerging, agent/fasternet.py:253) instead
   // of a dense (M, K) matrix: row m starts at (m * lda + (m / a_grp) * a_grp_jump) floats, and columns at or beyond
@@ -719,8 +720,10 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f32_kernel(const GemmGroup 
         }
         cs += __shfl_xor(cs, 32);
         cq += __shfl_xor(cq, 32);
-        if (kh == 0 && col_ok) {
-          float* o = P.cstat + (size_t)((m0 + wm * (BM / WM)) / 32 + i) * 2 * N + col;
+        // (a 32-row block that starts at or past M belongs to no row: cstat has (M+31)/32 blocks and it is not written)
+        const int rblk = (m0 + wm * (BM / WM)) / 32 + i;
+        if (kh == 0 && col_ok && rblk * 32 < M) {
+          float* o = P.cstat + (size_t)rblk * 2 * N + col;
           o[0] = cs;
           o[N] = cq;
         }
@@ -872,6 +875,13 @@ inline hipError_t launch_tile(const GemmGroup& g, hipStream_t s) {
   for (int i = 0; i < g.nprob; ++i) {
     vec = vec && g.p[i].a_vec && g.p[i].b_vec;
     if ((g.p[i].apro != APRO_NONE) != apro) return hipErrorInvalidValue;   // a group shares the prologue
+    // cstat and the head are defined on the STORED C, but interior 16-byte tiles apply mask / resid in their final store
+    // loop, after both were taken, while edge tiles apply them before: no caller combines them, so the pair is refused
+    // instead of computed two ways (tests/test_gemm_epilogues_gpu.py case 10).  Wider than strictly needed: with
+    // store_c = 0 or a C without 16-byte rows no tile takes the late path and the pair would be consistent, but nobody
+    // asks for that either, and one rule for every layout is easier to hold.  The rule holds for every caller of
+    // launch_tile, porl_gemm_f32 with its gemm_resid + gemm_cstat debug pointers included.
+    if (g.p[i].splitk <= 1 && (g.p[i].mask || g.p[i].resid) && (g.p[i].cstat || g.p[i].headw)) return hipErrorInvalidValue;
   }
   if (apro) {
     // affine + ReLU prologue: instantiated for the two tiles the encoder's W2 products use, 16-byte operands,

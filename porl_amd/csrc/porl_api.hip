@@ -1503,6 +1503,80 @@ int porl_gemm_f32(int mode, int tile, int32_t M, int32_t N, int32_t K, const flo
   return launch_group(g, tile, g_tune, s);
 }
 
+// Descriptor-level launch of one group (tests/test_gemm_epilogues_gpu.py): every caller-set field of GemmProb, validated
+// on the host so that nothing launch_tile would refuse, and nothing the kernel would silently ignore, reaches a launch.
+int porl_gemm_f32_group(const porl_gemm_desc* probs, int32_t nprob, int tile, int single_buffer, void* stream) {
+  if (!probs) PORL_FAIL(PORL_ERR_INVALID, "null descriptors");
+  if (nprob < 1 || nprob > MAX_GROUP) PORL_FAIL(PORL_ERR_INVALID, "nprob %d outside [1,%d]", nprob, MAX_GROUP);
+  if (tile < -1 || tile >= TILE_COUNT) PORL_FAIL(PORL_ERR_INVALID, "tile must be -1..%d", TILE_COUNT - 1);
+  GemmGroup g{};
+  g.nprob = nprob;
+  g.single_buffer = single_buffer != 0;
+  int n_apro = 0;
+  bool vec = true;
+  for (int i = 0; i < nprob; ++i) {
+    const porl_gemm_desc& d = probs[i];
+    if (d.mode < 0 || d.mode > 2) PORL_FAIL(PORL_ERR_INVALID, "problem %d: mode must be 0..2", i);
+    if (!d.A || !d.B || !d.C) PORL_FAIL(PORL_ERR_INVALID, "problem %d: null A, B or C", i);
+    if (d.M < 1 || d.N < 1 || d.K < 0) PORL_FAIL(PORL_ERR_INVALID, "problem %d: need M >= 1, N >= 1, K >= 0", i);
+    if (d.headw && !d.headout) PORL_FAIL(PORL_ERR_INVALID, "problem %d: headw without headout", i);
+    if (d.colsum && d.mode != GEMM_TN) PORL_FAIL(PORL_ERR_INVALID, "problem %d: colsum needs the TN layout (A stored (K, M))", i);
+    if (d.rscale && d.rs_rows < 1) PORL_FAIL(PORL_ERR_INVALID, "problem %d: rscale needs rs_rows >= 1", i);
+    if (d.rscale && !d.resid) PORL_FAIL(PORL_ERR_INVALID, "problem %d: rscale without resid", i);
+    const bool apro = d.a_colscale || d.a_colshift;
+    if (d.splitk > 1 && (d.bias || d.act || d.mask || d.headw || d.resid || d.cstat || apro))
+      PORL_FAIL(PORL_ERR_UNSUPPORTED, "problem %d: splitk > 1 writes raw slabs: no bias, act, mask, head, resid, cstat or prologue", i);
+    if ((d.mask || d.resid) && (d.cstat || d.headw))
+      PORL_FAIL(PORL_ERR_UNSUPPORTED, "problem %d: mask / resid together with cstat / head", i);
+    if (d.a_grp < 0 || (d.a_grp > 0 && (d.mode != GEMM_NT || d.a_seg_tiles < 1)))
+      PORL_FAIL(PORL_ERR_INVALID, "problem %d: a gathered A (a_grp > 0) needs the NT layout and a_seg_tiles >= 1", i);
+    if (d.reserved) PORL_FAIL(PORL_ERR_INVALID, "problem %d: reserved must be 0", i);
+    // extents: a leading dimension shorter than the contiguous extent aliases rows (a gathered A reads a_seg_tiles
+    // K-tiles per stored row, then jumps)
+    const int a_ext = d.mode == GEMM_TN ? d.M : (d.a_grp > 0 && d.a_seg_tiles * GEMM_BK < d.K ? d.a_seg_tiles * GEMM_BK : d.K);
+    const int b_ext = d.mode == GEMM_NT ? d.K : d.N;
+    if (d.lda < a_ext || d.ldb < b_ext || d.ldc < d.N)
+      PORL_FAIL(PORL_ERR_INVALID, "problem %d: lda %d / ldb %d / ldc %d below the contiguous extents %d / %d / %d", i,
+                d.lda, d.ldb, d.ldc, a_ext, b_ext, d.N);
+    if (d.mask && d.ldmask < d.N) PORL_FAIL(PORL_ERR_INVALID, "problem %d: ldmask %d < N", i, d.ldmask);
+    if (d.a_grp > 0 ? (d.lda < 1 || d.a_grp_jump < 0 || d.a_seg_jump < 0) : (d.a_grp_jump || d.a_seg_tiles || d.a_seg_jump))
+      PORL_FAIL(PORL_ERR_INVALID, "problem %d: a_grp_jump / a_seg_jump must be >= 0, and 0 (with a_seg_tiles) for a dense A", i);
+    GemmProb p = make_prob(d.mode, d.A, d.lda, d.B, d.ldb, d.C, d.ldc, d.M, d.N, d.K);
+    if (p.a_vec && (d.a_grp_jump % 4 || d.a_seg_jump % 4))     // the jumps move 16-byte loads
+      PORL_FAIL(PORL_ERR_INVALID, "problem %d: a_grp_jump / a_seg_jump must be multiples of 4 floats with a 16-byte-readable A", i);
+    p.bias = d.bias; p.act = d.act; p.mask = d.mask; p.ldmask = d.ldmask;
+    p.headw = d.headw; p.headout = d.headout; p.colsum = d.colsum;
+    p.resid = d.resid; p.rscale = d.rscale; p.rs_rows = d.rs_rows >= 1 ? d.rs_rows : 1; p.rs_row0 = d.rs_row0;
+    p.cstat = d.cstat;
+    p.a_grp = d.a_grp; p.a_grp_jump = d.a_grp_jump; p.a_seg_tiles = d.a_seg_tiles; p.a_seg_jump = d.a_seg_jump;
+    p.splitk = d.splitk > 1 ? d.splitk : 1;
+    p.store_c = d.store_c != 0;
+    if (apro) {
+      if (!d.a_colscale || !d.a_colshift) PORL_FAIL(PORL_ERR_INVALID, "problem %d: the prologue needs a_colscale and a_colshift", i);
+      if (d.mode != GEMM_NT) PORL_FAIL(PORL_ERR_UNSUPPORTED, "problem %d: the operand prologue exists for the NT layout only", i);
+      if (d.K % GEMM_BK) PORL_FAIL(PORL_ERR_UNSUPPORTED, "problem %d: the operand prologue needs K %% %d == 0", i, GEMM_BK);
+      if (!aligned16(d.a_colscale) || !aligned16(d.a_colshift))
+        PORL_FAIL(PORL_ERR_INVALID, "problem %d: a_colscale / a_colshift must be 16-byte aligned", i);
+      p.apro = APRO_AFFINE_RELU; p.a_colscale = d.a_colscale; p.a_colshift = d.a_colshift;
+      ++n_apro;
+    }
+    vec = vec && p.a_vec && p.b_vec;
+    g.p[i] = p;
+  }
+  if (tile < 0) tile = pick_tile(g, g_tune);
+  if (n_apro) {                      // what launch_tile refuses for the prologue instantiations
+    if (n_apro != nprob) PORL_FAIL(PORL_ERR_UNSUPPORTED, "a group shares the operand prologue: all problems or none");
+    if (tile != TILE_128x64 && tile != TILE_64x64 && tile != TILE_128x96)
+      PORL_FAIL(PORL_ERR_UNSUPPORTED, "the operand prologue exists on tiles 1, 3 and 4, not %d", tile);
+    if (!vec) PORL_FAIL(PORL_ERR_UNSUPPORTED, "the operand prologue needs 16-byte-readable operands");
+    const int max_k = g.single_buffer && tile == TILE_64x64 ? 512 : 1024;    // the scale / shift table lives in LDS
+    for (int i = 0; i < nprob; ++i)
+      if (g.p[i].K > max_k) PORL_FAIL(PORL_ERR_UNSUPPORTED, "problem %d: the operand prologue holds K <= %d", i, max_k);
+  }
+  DevGuard _dg(device_of(probs[0].C));
+  return launch_group(g, tile, g_tune, (hipStream_t)stream);
+}
+
 int porl_adam_ema(float* p, const float* g, float* m, float* v, float* target, int64_t n, double lr, int32_t step,
                   double beta1, double beta2, double eps, double ema_beta, void* stream) {
   if (!p || !g || !m || !v) PORL_FAIL(PORL_ERR_INVALID, "null buffer");

@@ -463,6 +463,27 @@ def gemm_f32(mode, A, B, M, N_, K, lda, ldb, C_out, ldc, bias=None, act=0, mask=
                                   N.current_stream_ptr(C_out)), "porl_gemm_f32")
 
 
+_GEMM_DESC_TENSORS = ("A", "B", "C", "bias", "mask", "headw", "headout", "colsum", "a_colscale", "a_colshift", "resid",
+                      "rscale", "cstat")
+
+
+def gemm_f32_group(descs, tile=-1, single_buffer=0):
+    """Test/utility entry: one launch of up to 8 products, see include/porl_hip.h:porl_gemm_f32_group.  Each descriptor
+    is a dict of porl_gemm_desc fields: torch tensors (or None) for the pointers, ints for the rest; store_c defaults
+    to 1, everything else to 0 / NULL."""
+    arr = (N.GemmDesc * max(len(descs), 1))()
+    for d, a in zip(descs, arr):
+        unknown = set(d) - {n for n, _ in N.GemmDesc._fields_}
+        if unknown:
+            raise KeyError(f"not porl_gemm_desc fields: {sorted(unknown)}")
+        a.store_c = 1
+        for k, v in d.items():
+            setattr(a, k, (None if v is None else v.data_ptr()) if k in _GEMM_DESC_TENSORS else int(v))
+    dev = descs[0].get("C") if descs else None
+    N.check(N.lib().porl_gemm_f32_group(arr, len(descs), tile, single_buffer, N.current_stream_ptr(dev)),
+            "porl_gemm_f32_group")
+
+
 def adam_ema(p, g, m, v, target, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, ema_beta=0.0):
     N.check(N.lib().porl_adam_ema(N.ptr(p), N.ptr(g), N.ptr(m), N.ptr(v), N.ptr(target), p.numel(), lr, step,
                                   beta1, beta2, eps, ema_beta, N.current_stream_ptr(p)), "porl_adam_ema")

@@ -148,6 +148,72 @@ int main() {
   REJECT(porl_grad_clip(x, 8, 1.f, x, nullptr, nullptr));
   REJECT(porl_gemm_f32(7, -1, 8, 8, 8, x, 8, x, 8, x, 8, nullptr, 0, nullptr, 0, 1, nullptr, nullptr));
   REJECT(porl_gemm_f32(0, -1, 8, 8, 8, nullptr, 8, x, 8, x, 8, nullptr, 0, nullptr, 0, 1, nullptr, nullptr));
+  {
+    // porl_gemm_f32_group: every refusal happens before anything is launched (x stands in for device buffers)
+    porl_gemm_desc d{};
+    d.A = P[2]; d.B = P[3]; d.C = P[4]; d.mode = 0; d.M = 8; d.N = 8; d.K = 32; d.lda = 32; d.ldb = 32; d.ldc = 8; d.store_c = 1;
+    porl_gemm_desc nine[9];
+    for (porl_gemm_desc& e : nine) e = d;
+    REJECT(porl_gemm_f32_group(nullptr, 1, 3, 0, nullptr));
+    REJECT(porl_gemm_f32_group(&d, 0, 3, 0, nullptr));
+    REJECT(porl_gemm_f32_group(nine, 9, 3, 0, nullptr));                                       // MAX_GROUP is 8
+    REJECT(porl_gemm_f32_group(&d, 1, 5, 0, nullptr));                                         // tile out of range
+    REJECT(porl_gemm_f32_group(&d, 1, -2, 0, nullptr));
+    { porl_gemm_desc b = d; b.mode = 3; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.A = nullptr; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.B = nullptr; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.C = nullptr; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.M = 0; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.N = 0; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.K = -1; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.headw = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }             // no headout
+    { porl_gemm_desc b = d; b.colsum = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }            // k-contiguous A (NT)
+    { porl_gemm_desc b = d; b.mode = 1; b.colsum = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); } // ... and NN
+    { porl_gemm_desc b = d; b.resid = x; b.rscale = x; b.rs_rows = 0; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.rscale = x; b.rs_rows = 4; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }   // no resid
+    // splitk > 1 writes raw slabs: every epilogue is refused with it
+    { porl_gemm_desc b = d; b.splitk = 2; b.bias = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.splitk = 2; b.act = 1; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.splitk = 2; b.mask = x; b.ldmask = 8; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.splitk = 2; b.headw = x; b.headout = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.splitk = 2; b.resid = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.splitk = 2; b.cstat = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    // cstat / head are defined on the stored C: refused together with mask / resid
+    { porl_gemm_desc b = d; b.mask = x; b.ldmask = 8; b.cstat = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.mask = x; b.ldmask = 8; b.headw = x; b.headout = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.resid = x; b.cstat = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.resid = x; b.headw = x; b.headout = x; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    // gathered A: NT and a_seg_tiles >= 1 only
+    { porl_gemm_desc b = d; b.a_grp = 5; b.a_seg_tiles = 0; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.a_grp = 5; b.a_seg_tiles = 1; b.mode = 1; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.a_grp = -1; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.a_grp = 5; b.a_seg_tiles = 1; b.a_grp_jump = -32; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.a_grp = 5; b.a_seg_tiles = 1; b.a_seg_jump = -32; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.a_grp = 5; b.a_seg_tiles = 1; b.a_grp_jump = 6; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }   // moves 16-byte loads
+    { porl_gemm_desc b = d; b.a_grp = 5; b.a_seg_tiles = 1; b.a_seg_jump = 2; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.a_seg_jump = 32; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }         // dense A: would be ignored
+    // extents
+    { porl_gemm_desc b = d; b.ldc = 7; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.lda = 31; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.ldb = 31; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.mode = 2; b.lda = 7; b.ldb = 8; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }   // TN: A is (K, M)
+    { porl_gemm_desc b = d; b.mode = 1; b.ldb = 7; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }              // NN: B is (K, N)
+    { porl_gemm_desc b = d; b.mask = x; b.ldmask = 7; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = d; b.reserved = 1; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    // what launch_tile refuses for the operand prologue, as error codes
+    porl_gemm_desc ap = d;
+    ap.a_colscale = P[0]; ap.a_colshift = P[1];
+    REJECT(porl_gemm_f32_group(&ap, 1, 0, 0, nullptr));                                        // tiles 0 and 2 have no prologue
+    REJECT(porl_gemm_f32_group(&ap, 1, 2, 0, nullptr));
+    { porl_gemm_desc b = ap; b.a_colshift = nullptr; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = ap; b.K = 100; b.lda = b.ldb = 100; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }   // K % 32
+    { porl_gemm_desc b = ap; b.K = 1056; b.lda = b.ldb = 1056; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); } // LDS table: K <= 1024
+    { porl_gemm_desc b = ap; b.K = 544; b.lda = b.ldb = 544; REJECT(porl_gemm_f32_group(&b, 1, 3, 1, nullptr)); }   // single buffer: K <= 512
+    { porl_gemm_desc b = ap; b.mode = 1; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc b = ap; b.lda = 33; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }               // no 16-byte loads
+    { porl_gemm_desc b = ap; b.a_colscale = P[0] + 1; REJECT(porl_gemm_f32_group(&b, 1, 3, 0, nullptr)); }
+    { porl_gemm_desc two[2] = {ap, d}; REJECT(porl_gemm_f32_group(two, 2, 3, 0, nullptr)); }                // mixed prologue in a group
+  }
   REJECT(porl_tune_set(nullptr, 1));
   REJECT(porl_tune_set("no_such_key", 1));
   ACCEPT(porl_tune_set("skinny", 7));
