@@ -339,6 +339,34 @@ int porl_qnet_learn_variant(porl_qnet* h, const float* states, int64_t s_rs, con
                             const float* rewards, const float* next_states, int64_t n_rs, const float* dones,
                             const int64_t* idx, int32_t batch, const porl_qnet_hyper* hp,
                             const porl_qnet_variant* variant, void* stream);
+/* porl_qnet_learn_sampled with a porl_qnet_variant (non-NULL): the rows are drawn inside the step kernel and the variant's
+ * loss is applied to them — td_off for the behaviour-policy pre-training of bcq.py:23-47, next_mask / is_weights /
+ * td_abs indexed by minibatch position as in porl_qnet_learn_variant. */
+int porl_qnet_learn_sampled_variant(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions,
+                                    const float* rewards, const float* next_states, int64_t n_rs, const float* dones,
+                                    int64_t n_rows, uint64_t seed, uint64_t draw, int32_t batch, const porl_qnet_hyper* hp,
+                                    const porl_qnet_variant* variant, void* stream);
+/* Discrete BCQ (src/porl/policy/bcq.py:50-86) from one call.  `beh` is a second engine that holds the behaviour policy
+ * (src/porl/net/behavior_policy.py) as its online parameters; it must agree with `h` on state_dim and n_actions.
+ *   porl_qnet_bcq_mask: mask_out[b, j] = softmax(beh(next_states[idx[b]]))[j] > threshold ? 1 : 0, (batch, n_actions)
+ *     fp32 by minibatch position — one launch (csrc/bcq_mask.hpp) when porl_qnet_one_launch(beh), else gather, one launch
+ *     per layer and porl_softmax_mask's kernel.  Nothing past batch * n_actions floats is written.
+ *   porl_qnet_bcq_learn: that mask into h's workspace, then porl_qnet_learn_variant on rows idx with next_mask set
+ *     (one-launch step kernel + reduction/Adam, or the multi-launch path for wide Q networks).  A row whose mask is all
+ *     zero bootstraps from action 0, as torch.argmax does on the tie.
+ *   porl_qnet_bcq_learn_sampled: the same with batch row b = row perm_{seed,draw}(b) of [0, n_rows) drawn inside both
+ *     kernels (porl_sample_indices' permutation); needs porl_qnet_can_sample(h), else PORL_ERR_UNSUPPORTED.
+ * Null pointers, batch outside [1, max_batch] of either engine, engines that disagree on state_dim / n_actions, row
+ * strides below state_dim and a non-finite threshold are PORL_ERR_INVALID, checked before anything is launched. */
+int porl_qnet_bcq_mask(porl_qnet* beh, const float* next_states, int64_t n_rs, const int64_t* idx, int32_t batch,
+                       float threshold, float* mask_out, void* stream);
+int porl_qnet_bcq_learn(porl_qnet* h, porl_qnet* beh, const float* states, int64_t s_rs, const int64_t* actions,
+                        const float* rewards, const float* next_states, int64_t n_rs, const float* dones,
+                        const int64_t* idx, int32_t batch, const porl_qnet_hyper* hp, float threshold, void* stream);
+int porl_qnet_bcq_learn_sampled(porl_qnet* h, porl_qnet* beh, const float* states, int64_t s_rs, const int64_t* actions,
+                                const float* rewards, const float* next_states, int64_t n_rs, const float* dones,
+                                int64_t n_rows, uint64_t seed, uint64_t draw, int32_t batch, const porl_qnet_hyper* hp,
+                                float threshold, void* stream);
 /* One learn step of a distributional trainer (src/porl/train/qr_dqn_trainer.py:97-222, c51_trainer.py:52-174) on the
  * minibatch { row idx[b] (or b when idx is NULL) of the given replay arrays : b < batch } from one call: gather into the
  * staging buffers, the forwards as one grouped launch per layer (online net on s with its activations kept, target net

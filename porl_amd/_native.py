@@ -30,6 +30,7 @@ SYMBOLS = [
     "porl_qnet_cql_backward", "porl_qnet_apply", "porl_qnet_learn", "porl_qnet_sync_target",
     "porl_qnet_forward", "porl_qnet_forward_loaded", "porl_qnet_backward", "porl_qr_loss", "porl_iqn_quantile_huber", "porl_iqn_cos_embed", "porl_iqn_hadamard", "porl_iqn_hadamard_backward", "porl_iqn_select", "porl_iqn_scatter", "porl_iqn_target", "porl_grad_clip", "porl_c51_loss", "porl_reduce_mean", "porl_qnet_penalty", "porl_qnet_learn_indexed", "porl_qnet_one_launch", "porl_qnet_learn_variant", "porl_qnet_can_sample", "porl_qnet_learn_sampled", "porl_qnet_dist_learn",
     "porl_qnet_record", "porl_qnet_act_ok", "porl_qnet_act",
+    "porl_qnet_learn_sampled_variant", "porl_qnet_bcq_mask", "porl_qnet_bcq_learn", "porl_qnet_bcq_learn_sampled",
     "porl_iqn_create", "porl_iqn_destroy", "porl_iqn_workspace_floats", "porl_iqn_bind", "porl_iqn_learn", "porl_iqn_act",
     "porl_iqn_mix", "porl_iqn_head",
     "porl_enc_create", "porl_enc_destroy", "porl_enc_param_floats", "porl_enc_stat_floats",
@@ -212,6 +213,12 @@ def _declare(lib):
     lib.porl_qnet_can_sample.restype = i32
     lib.porl_qnet_learn_sampled.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, i64, C.c_uint64, C.c_uint64, i32,
                                             C.POINTER(QnetHyper), vp]
+    lib.porl_qnet_learn_sampled_variant.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, i64, C.c_uint64, C.c_uint64, i32,
+                                                    C.POINTER(QnetHyper), C.POINTER(QnetVariant), vp]
+    lib.porl_qnet_bcq_mask.argtypes = [vp, vp, i64, vp, i32, f32, vp, vp]
+    lib.porl_qnet_bcq_learn.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, C.POINTER(QnetHyper), f32, vp]
+    lib.porl_qnet_bcq_learn_sampled.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, vp, i64, C.c_uint64, C.c_uint64, i32,
+                                                C.POINTER(QnetHyper), f32, vp]
     lib.porl_qnet_sync_target.argtypes = [vp, vp]
     lib.porl_qnet_forward.argtypes = [vp, C.c_int, vp, i64, i32, vp, i64, vp]
     lib.porl_qnet_forward_loaded.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i64, vp]

@@ -22,6 +22,7 @@
 #include "dist_losses.hpp"
 #include "online.hpp"
 #include "per_online.hpp"
+#include "bcq_mask.hpp"
 
 using namespace porl;
 
@@ -1896,6 +1897,7 @@ struct porl_qnet {
     int64_t xs, xn, rew, done, actions;                  // actions: int64 stored in 2 floats each
     int64_t act[PORL_MAX_HIDDEN + 1], tmp[2], dz[2], slab, part_td, part_pen, fslab, total;
     int64_t tmp2[2], row_loss;                           // porl_qnet_dist_learn: third forward's ping-pong, per-row losses
+    int64_t mask;                                        // porl_qnet_bcq_learn*: (max_batch, n_actions) behaviour mask
   } ws;
   // one-launch path (qnet_fused.hpp): every width <= 128, at most QF_MAX_LIN Linear layers, LDS plan fits
   bool fused_ok = false;
@@ -2008,6 +2010,7 @@ int porl_qnet_create(const porl_qnet_cfg* c, porl_qnet** out) {
   // appended behind everything older, so every earlier offset keeps its meaning
   h->ws.tmp2[0] = take((int64_t)B * maxld); h->ws.tmp2[1] = take((int64_t)B * maxld);
   h->ws.row_loss = take(B);
+  h->ws.mask = take((int64_t)B * c->n_actions);
   h->ws.total = o;
   *out = h;
   return PORL_OK;
@@ -2566,6 +2569,149 @@ int porl_qnet_learn_variant(porl_qnet* h, const float* states, int64_t s_rs, con
     return qnet_general_learn(h, hp, variant, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, idx, (hipStream_t)stream);
   return qnet_fused_backward(h, hp, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, idx,
                              (hipStream_t)stream, true, variant);
+}
+
+int porl_qnet_learn_sampled_variant(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
+                                    const float* next_states, int64_t n_rs, const float* dones, int64_t n_rows, uint64_t seed,
+                                    uint64_t draw, int32_t batch, const porl_qnet_hyper* hp, const porl_qnet_variant* variant,
+                                    void* stream) {
+  if (!h) PORL_FAIL(PORL_ERR_INVALID, "null engine");
+  if (!hp || !states || !actions || !rewards || !next_states || !dones || !variant) PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  if (batch < 1 || batch > h->cfg.max_batch) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", batch, h->cfg.max_batch);
+  if (n_rows < batch || n_rows > (int64_t(1) << 40)) PORL_FAIL(PORL_ERR_INVALID, "need batch <= n_rows <= 2^40");
+  PORL_TRY(qnet_ready(h, false)); DevGuard _dg(h->device);
+  if (!porl_qnet_can_sample(h)) PORL_FAIL(PORL_ERR_UNSUPPORTED, "in-kernel sampling needs the two-group one-launch step kernel");
+  QnetSampling sp;
+  sp.n_rows = n_rows; sp.seed = seed; sp.step = draw;
+  return qnet_fused_backward(h, hp, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, nullptr,
+                             (hipStream_t)stream, true, variant, &sp);
+}
+
+// ---- discrete BCQ from one call (csrc/bcq_mask.hpp) -------------------------------------------------------------------
+// mask[b, :] of the behaviour engine `beh` on rows idx[b] (samp: the keyed permutation's rows) of next_states.  One launch
+// when beh's network fits one block's LDS (beh->fused_ok), else [sampler,] gather, one launch per layer and
+// softmax_mask_kernel — the launches of BehaviorPolicy.sample on the gathered rows, the same numbers.
+static int bcq_mask_launch(porl_qnet* beh, const float* next_states, int64_t n_rs, const int64_t* idx, int B, float threshold,
+                           float* mask_out, const QnetSampling* samp, hipStream_t s) {
+  const int L = beh->cfg.n_hidden, A = beh->cfg.n_actions, S = beh->cfg.state_dim;
+  const bool sampled = samp && samp->n_rows > 0;
+  if (beh->fused_ok && beh->tune.qnet_fused) {
+    BcqMaskArgs a{};
+    a.params = beh->buf.params; a.next_states = next_states; a.n_rs = (long)n_rs; a.idx = sampled ? nullptr : idx;
+    a.mask = mask_out; a.B = B; a.n_lin = L + 1; a.threshold = threshold;
+    int maxw = 0, wmax = 0;
+    for (int l = 0; l <= L + 1; ++l) { a.dims[l] = beh->net.dims[l]; if (l > 0) maxw = std::max(maxw, (a.dims[l] + 31) & ~31); }
+    for (int l = 0; l <= L; ++l) {
+      a.w_off[l] = beh->net.w[l];
+      wmax = std::max(wmax, ((a.dims[l + 1] + 31) & ~31) * (((a.dims[l] + 15) & ~15) + 4 + 1));     // image + bias row
+    }
+    int off = 0;
+    a.lds_rows = off; off += 2 * QF_ROWS;
+    a.lds_x = off; off += QF_ROWS * (((S + 31) & ~31) + 4);
+    a.lds_act[0] = off; off += QF_ROWS * (maxw + 4);
+    a.lds_act[1] = off; off += QF_ROWS * (maxw + 4);
+    a.lds_w = off; off += wmax;
+    const int lds_bytes = off * (int)sizeof(float);     // below the step kernel's own plan, which fused_ok vouches for
+    if (lds_bytes > QF_MAX_LDS_BYTES) PORL_FAIL(PORL_ERR_UNSUPPORTED, "behaviour network needs %d bytes of LDS", lds_bytes);
+    if (sampled) { a.samp_n = samp->n_rows; a.samp_seed = samp->seed; a.samp_step = samp->step; a.samp_hb = feistel_half_bits(samp->n_rows); }
+    static bool attr_set = false;
+    if (!attr_set) {
+      PORL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcq_mask_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   QF_MAX_LDS_BYTES));
+      attr_set = true;
+    }
+    double macs = 0;
+    for (int l = 0; l <= L; ++l) macs += (double)a.dims[l] * a.dims[l + 1];
+    ProfScope ps("bcq_mask_kernel", s, 2.0 * B * macs, 4.0 * B * (S + A));
+    hipLaunchKernelGGL(bcq_mask_kernel, dim3(cdiv(B, QF_ROWS)), dim3(256), (size_t)lds_bytes, s, a);
+    PORL_HIP(hipGetLastError());
+    return PORL_OK;
+  }
+  float* W = beh->buf.workspace;
+  if (sampled) {
+    int64_t* drawn = reinterpret_cast<int64_t*>(W + beh->ws.actions);       // (max_batch) int64 of staging space
+    hipLaunchKernelGGL(sample_indices_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, samp->n_rows, B, samp->seed, samp->step,
+                       feistel_half_bits(samp->n_rows), (int64_t)0, (int64_t)0, drawn);
+    PORL_HIP(hipGetLastError());
+    idx = drawn;
+  }
+  hipLaunchKernelGGL(bcq_gather_kernel, dim3((unsigned)(((long)B * beh->Sp + 255) / 256)), dim3(256), 0, s, next_states, (long)n_rs,
+                     idx, W + beh->ws.xs, B, S, beh->Sp);
+  PORL_HIP(hipGetLastError());
+  beh->batch = 0;
+  float* dst[1][PORL_MAX_HIDDEN + 1];
+  for (int l = 0; l <= L; ++l) dst[0][l] = W + beh->ws.tmp[l & 1];
+  const float* params[1] = {beh->buf.params};
+  const float* inputs[1] = {W + beh->ws.xs};
+  PORL_TRY(qnet_forward(beh, 1, params, inputs, dst, B, s));
+  hipLaunchKernelGGL(softmax_mask_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, dst[0][L], (long)beh->ld[L], B, A, threshold, 0,
+                     mask_out);
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+int porl_qnet_bcq_mask(porl_qnet* beh, const float* next_states, int64_t n_rs, const int64_t* idx, int32_t batch,
+                       float threshold, float* mask_out, void* stream) {
+  if (!beh) PORL_FAIL(PORL_ERR_INVALID, "null engine");
+  if (!next_states || !idx || !mask_out) PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  if (batch < 1 || batch > beh->cfg.max_batch) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", batch, beh->cfg.max_batch);
+  if (n_rs < beh->cfg.state_dim) PORL_FAIL(PORL_ERR_INVALID, "row stride below state_dim %d", beh->cfg.state_dim);
+  if (!std::isfinite(threshold)) PORL_FAIL(PORL_ERR_INVALID, "threshold is not finite");
+  PORL_TRY(qnet_ready(beh, false)); DevGuard _dg(beh->device);
+  return bcq_mask_launch(beh, next_states, n_rs, idx, batch, threshold, mask_out, nullptr, (hipStream_t)stream);
+}
+
+static int bcq_learn_check(const porl_qnet* h, const porl_qnet* beh, const void* const* ptrs, int nptrs, int32_t batch,
+                           int64_t s_rs, int64_t n_rs, float threshold) {
+  if (!h || !beh) PORL_FAIL(PORL_ERR_INVALID, "null engine");
+  for (int i = 0; i < nptrs; ++i)
+    if (!ptrs[i]) PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  const int mb = std::min(h->cfg.max_batch, beh->cfg.max_batch);
+  if (batch < 1 || batch > mb) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", batch, mb);
+  if (beh->cfg.state_dim != h->cfg.state_dim || beh->cfg.n_actions != h->cfg.n_actions)
+    PORL_FAIL(PORL_ERR_INVALID, "behaviour network (%d -> %d) does not match the Q network (%d -> %d)", beh->cfg.state_dim,
+              beh->cfg.n_actions, h->cfg.state_dim, h->cfg.n_actions);
+  if (s_rs < h->cfg.state_dim || n_rs < h->cfg.state_dim) PORL_FAIL(PORL_ERR_INVALID, "row stride below state_dim %d", h->cfg.state_dim);
+  if (!std::isfinite(threshold)) PORL_FAIL(PORL_ERR_INVALID, "threshold is not finite");
+  PORL_TRY(qnet_ready(h, false));
+  PORL_TRY(qnet_ready(beh, false));
+  if (beh->device != h->device) PORL_FAIL(PORL_ERR_INVALID, "the two engines live on different devices");
+  return PORL_OK;
+}
+
+int porl_qnet_bcq_learn(porl_qnet* h, porl_qnet* beh, const float* states, int64_t s_rs, const int64_t* actions,
+                        const float* rewards, const float* next_states, int64_t n_rs, const float* dones, const int64_t* idx,
+                        int32_t batch, const porl_qnet_hyper* hp, float threshold, void* stream) {
+  const void* ptrs[] = {states, actions, rewards, next_states, dones, idx, hp};
+  PORL_TRY(bcq_learn_check(h, beh, ptrs, 7, batch, s_rs, n_rs, threshold));
+  DevGuard _dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  float* mask = h->buf.workspace + h->ws.mask;
+  PORL_TRY(bcq_mask_launch(beh, next_states, n_rs, idx, batch, threshold, mask, nullptr, s));
+  porl_qnet_variant var{};
+  var.next_mask = mask;
+  if (!h->fused_ok || !h->tune.qnet_fused)
+    return qnet_general_learn(h, hp, &var, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, idx, s);
+  return qnet_fused_backward(h, hp, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, idx, s, true, &var);
+}
+
+int porl_qnet_bcq_learn_sampled(porl_qnet* h, porl_qnet* beh, const float* states, int64_t s_rs, const int64_t* actions,
+                                const float* rewards, const float* next_states, int64_t n_rs, const float* dones,
+                                int64_t n_rows, uint64_t seed, uint64_t draw, int32_t batch, const porl_qnet_hyper* hp,
+                                float threshold, void* stream) {
+  const void* ptrs[] = {states, actions, rewards, next_states, dones, hp};
+  PORL_TRY(bcq_learn_check(h, beh, ptrs, 6, batch, s_rs, n_rs, threshold));
+  if (n_rows < batch || n_rows > (int64_t(1) << 40)) PORL_FAIL(PORL_ERR_INVALID, "need batch <= n_rows <= 2^40");
+  if (!porl_qnet_can_sample(h)) PORL_FAIL(PORL_ERR_UNSUPPORTED, "in-kernel sampling needs the two-group one-launch step kernel");
+  DevGuard _dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  QnetSampling sp;
+  sp.n_rows = n_rows; sp.seed = seed; sp.step = draw;
+  float* mask = h->buf.workspace + h->ws.mask;
+  PORL_TRY(bcq_mask_launch(beh, next_states, n_rs, nullptr, batch, threshold, mask, &sp, s));
+  porl_qnet_variant var{};
+  var.next_mask = mask;
+  return qnet_fused_backward(h, hp, batch, states, s_rs, next_states, n_rs, actions, rewards, dones, nullptr, s, true, &var, &sp);
 }
 
 // ---- one learn step of the distributional trainers from one call (QR-DQN, C51: dist_losses.hpp) -------------------------

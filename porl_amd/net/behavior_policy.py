@@ -17,11 +17,12 @@ class BehaviorPolicy(nn.Module):
     def __init__(self, state_size: int, action_size: int, hidden_sizes: List[int] = [64, 128]):
         super().__init__()
         self.action_size = action_size
-        self.network = nn.Sequential(
-            nn.Linear(state_size, hidden_sizes[0]), nn.ReLU(),
-            nn.Linear(hidden_sizes[0], hidden_sizes[1]), nn.ReLU(),
-            nn.Linear(hidden_sizes[1], action_size),
-        )
+        # (any number of hidden layers; the default two give the reference's network.0 / .2 / .4)
+        layers, width = [], state_size
+        for h in hidden_sizes:
+            layers += [nn.Linear(width, h), nn.ReLU()]
+            width = h
+        self.network = nn.Sequential(*layers, nn.Linear(width, action_size))
         self._spec = (state_size, action_size, list(hidden_sizes))
         self._engine = None
 

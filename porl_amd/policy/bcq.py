@@ -8,6 +8,14 @@ argument like upstream (`agent.train(env, bcq_learn, dataset=collect_dataset, pr
       behaviour policy allows in s' (probability > threshold): mask from `BehaviorPolicy.sample`, masked argmax
       inside the step kernel (`next_mask`).
 Minibatches come from `agent.replay_buffer.sample` (numpy's index stream, like the reference).
+
+Device-rows forms (extensions; one native call per step, csrc/bcq_mask.hpp):
+  bcq_learn_rows(agent, idx)           : bcq_learn's rule on rows `idx` (device int64) of the replay mirror — the mask
+      kernel reads the rows itself, the step kernel gathers them; no gather launches, no mask round trip through torch.
+  bcq_learn_device_sampled(agent, seed): the rows drawn on the device (the keyed permutation of engine.sample_indices),
+      inside both kernels when the Q engine can sample.
+  bcq_pretrain_device_sampled(agent, seed): `num_epochs` cross-entropy steps on device-drawn rows, one readback at the end.
+With a data-parallel exchange active all three gather the rows and take the paths above.
 """
 from __future__ import annotations
 
@@ -66,3 +74,94 @@ def bcq_learn(agent) -> float:
         return stats[:3]
     loss, agent.last_td_loss, _ = stats[:3].tolist()
     return loss
+
+
+# -- device-rows forms ----------------------------------------------------------------------------------------------------
+def _hyper(agent, eng, opt, alpha, B):
+    opt.step_count += 1
+    g = opt.param_groups[0]
+    return eng.hyper(agent.gamma, alpha, 1.0 / B, opt.step_count, g["lr"], g["betas"], g["eps"])
+
+
+def _learn_gathered(agent, idx):
+    """Today's pieces on the gathered rows (data-parallel exchange active: the step must not be fused into one call)."""
+    batch = agent.replay_buffer.gather_device(idx)
+    mask = agent.behavior_policy.sample(batch[3], agent.threshold)
+    var = N.QnetVariant(0, None, None, None, mask.data_ptr(), 0)
+    return _step(agent, agent._engine, agent.optimizer, batch, 0.0, var)
+
+
+def _loss_out(agent, stats):
+    if agent.async_losses:
+        return stats[:3]
+    loss, agent.last_td_loss, _ = stats[:3].tolist()
+    return loss
+
+
+def _launch_rows(agent, idx):
+    rb = agent.replay_buffer
+    if agent._exchange.active:
+        return _learn_gathered(agent, idx)
+    eng, m = agent._engine, rb._mirror
+    hp = _hyper(agent, eng, agent.optimizer, 0.0, idx.numel())
+    eng.bcq_learn_indexed(agent._behavior_engine, hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"],
+                          idx, agent.threshold)
+    return eng.stats
+
+
+def bcq_learn_rows(agent, idx):
+    """bcq_learn on rows `idx` (device int64) of the replay mirror -> loss (float, or the device statistics view with
+    agent.async_losses)."""
+    agent.replay_buffer._sync_mirror()
+    return _loss_out(agent, _launch_rows(agent, idx))
+
+
+def _next_draw(agent, batch):
+    rb = agent.replay_buffer
+    if batch > rb.size:
+        raise ValueError("Cannot take a larger sample than population when 'replace=False'")
+    rb._sync_mirror()
+    agent._draws = getattr(agent, "_draws", 0)
+    agent._draws += 1
+    return agent._draws - 1
+
+
+def bcq_learn_device_sampled(agent, seed=0):
+    """bcq_learn with the B distinct rows drawn on the device (draw counter shared with learn_device_sampled)."""
+    from .. import engine as E
+    rb, eng, B = agent.replay_buffer, agent._engine, agent.batch_size
+    draw = _next_draw(agent, B)
+    if agent._exchange.active or not eng.can_sample:
+        idx = E.sample_indices(rb.size, B, seed, draw, device=agent.device)
+        return _loss_out(agent, _launch_rows(agent, idx))
+    m = rb._mirror
+    hp = _hyper(agent, eng, agent.optimizer, 0.0, B)
+    eng.bcq_learn_sampled(agent._behavior_engine, hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"],
+                          rb.size, B, seed, draw, agent.threshold)
+    return _loss_out(agent, eng.stats)
+
+
+def bcq_pretrain_device_sampled(agent, seed=0):
+    """bcq_behavior_pretrain on device-drawn rows -> list of the per-epoch cross-entropy losses.  Each epoch's statistic
+    is copied device to device into a (num_epochs,) log that is read back once at the end."""
+    from .. import engine as E
+    rb, eng, B = agent.replay_buffer, agent._behavior_engine, agent.batch_size
+    ln_a = math.log(agent.action_size)
+    var = N.QnetVariant(0, None, None, None, None, 1)                  # td_off: loss = penalty = CE - ln A
+    log = torch.zeros(max(agent.num_epochs, 1), dtype=torch.float32, device=eng.device)
+    for epoch in range(agent.num_epochs):
+        draw = _next_draw(agent, B)
+        if agent._exchange.active:
+            idx = E.sample_indices(rb.size, B, seed, draw, device=agent.device)
+            _step(agent, eng, agent.behavior_optimizer, rb.gather_device(idx), 1.0, var)
+        else:
+            m = rb._mirror
+            hp = _hyper(agent, eng, agent.behavior_optimizer, 1.0, B)
+            args = (m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"])
+            if eng.can_sample:
+                eng.learn_sampled_variant(hp, *args, rb.size, B, seed, draw, var)
+            else:
+                idx = E.sample_indices(rb.size, B, seed, draw, device=agent.device)
+                eng.learn_indexed(hp, *args, idx, variant=var)
+        log[epoch:epoch + 1].copy_(eng.stats[2:3])
+    return [v + ln_a for v in log[:agent.num_epochs].tolist()]

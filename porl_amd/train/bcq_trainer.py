@@ -32,10 +32,33 @@ class BCQTrainer(DQNTrainer):
         self.behavior_optimizer = _FlatAdam(eng, list(self.behavior_policy.parameters()), 0.0005)
 
     def train(self, env, policy, num_episodes=1000, max_steps=1000, **kwargs):
-        """bcq_trainer.py:64-82: optional dataset collection and behaviour pre-training, then the online loop (which
-        needs an environment and is outside this package's scope: offline use goes through `train_offline`)."""
+        """bcq_trainer.py:64-82: optional dataset collection and behaviour pre-training, then the training loop.
+        Upstream ends in `super().train(env, policy, num_episodes, max_steps)`, a method DQNTrainer does not have; the
+        argument list is train_online's, whose loop calls `policy()` without arguments.  With `policy=bcq_learn` (the
+        function object, as scripts/train_bcq.py passes it) this is read as the online loop with bcq_learn bound to
+        this trainer.  Any other policy keeps the offline loop: `train_offline(policy, num_episodes)`."""
+        from ..policy.bcq import bcq_learn
         if "dataset" in kwargs:
             kwargs["dataset"](env, self)
         if "pretrain" in kwargs:
             kwargs["pretrain"](self)
+        if policy is bcq_learn:
+            return self.train_online(env, bcq_learn, num_episodes, max_steps)
         return self.train_offline(policy=policy, num_iterations=num_episodes)
+
+    def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
+        """dqn_trainer.py:119-180.  `policy=bcq_learn` (the function of porl_amd.policy.bcq): the loop with the BCQ rule
+        bound to this trainer — greedy act and record on their one-launch forms, each learn step numpy's index draw into
+        bcq_learn_rows (one native call: mask kernel, step kernel, reduction + Adam), the loss deferred; off the fast
+        path the reference loop with `lambda: bcq_learn(self)`.  Any other policy: DQNTrainer.train_online."""
+        from . import online
+        from ..policy import bcq
+        if policy is not bcq.bcq_learn:
+            return super().train_online(env, policy, num_episodes, max_steps)
+        cls = type(self)
+        fast = None
+        if online.fast_ok(self) and cls._act_for is cls.select_action and cls._greedy_for is cls.get_action and \
+                not self._exchange.active:
+            fast = online._FastBCQ(self)
+        return online.run(self, env, None if fast is not None else (lambda: bcq.bcq_learn(self)), num_episodes, max_steps,
+                          self.training_learning_step, self.replay_buffer, self.replay_buffer.push, fast)

@@ -168,6 +168,79 @@ class QnetEngine:
         self._stepped(hp)
         return batch
 
+    def _check_replay(self, states, actions, rewards, next_states, dones, n_rows, batch, idx=None):
+        """The checks learn_indexed / learn_sampled make inline (those two are left as they were on purpose: every other
+        trainer calls them), shared by the entry points below."""
+        if batch > self.cfg.max_batch:
+            raise RuntimeError(f"batch {batch} exceeds engine max_batch {self.cfg.max_batch}")
+        for name, x, dt in (("states", states, torch.float32), ("next_states", next_states, torch.float32),
+                            ("actions", actions, torch.int64), ("rewards", rewards, torch.float32),
+                            ("dones", dones, torch.float32)):
+            if x.dtype != dt or x.device != self.device or not x.is_contiguous() or x.shape[0] < n_rows:
+                raise RuntimeError(f"{name}: need a contiguous {dt} tensor of >= {n_rows} rows on {self.device}")
+        if states.shape[1:].numel() != self.cfg.state_dim or next_states.shape != states.shape:
+            raise RuntimeError("replay arrays do not match the network's state_dim")
+        if idx is not None and (idx.dtype != torch.int64 or idx.device != self.device or not idx.is_contiguous()):
+            raise RuntimeError(f"idx: need a contiguous torch.int64 tensor on {self.device}")
+
+    def learn_sampled_variant(self, hp, states, actions, rewards, next_states, dones, n_rows, batch, seed, draw, variant):
+        """learn_sampled with a QnetVariant (porl_qnet_learn_sampled_variant), e.g. td_off for BCQ's pre-training."""
+        self._ensure_bound()
+        self._check_replay(states, actions, rewards, next_states, dones, n_rows, batch)
+        N.check(self._lib.porl_qnet_learn_sampled_variant(
+            self._h, N.ptr(states), self.cfg.state_dim, N.ptr(actions), N.ptr(rewards), N.ptr(next_states),
+            self.cfg.state_dim, N.ptr(dones), int(n_rows), int(seed), int(draw), int(batch), C.byref(hp), C.byref(variant),
+            N.current_stream_ptr(self.device)), "porl_qnet_learn_sampled_variant")
+        self._stepped(hp)
+        return batch
+
+    # -- discrete BCQ (csrc/bcq_mask.hpp): `self` holds the behaviour policy in bcq_mask, the Q-networks in bcq_learn_* ----
+    def bcq_mask(self, next_states, idx, threshold, out=None):
+        """(B, A) fp32 0/1 mask of the actions whose behaviour probability in next_states[idx[b]] exceeds `threshold`
+        (porl_qnet_bcq_mask; this engine's online parameters are the behaviour policy)."""
+        self._ensure_bound()
+        B, A = idx.numel(), self.cfg.n_actions
+        if next_states.dtype != torch.float32 or next_states.device != self.device or not next_states.is_contiguous() or \
+                next_states.shape[1:].numel() != self.cfg.state_dim:
+            raise RuntimeError(f"next_states: need contiguous float32 rows of {self.cfg.state_dim} on {self.device}")
+        if idx.dtype != torch.int64 or idx.device != self.device or not idx.is_contiguous():
+            raise RuntimeError(f"idx: need a contiguous torch.int64 tensor on {self.device}")
+        if out is None:
+            out = torch.empty(B, A, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() or out.numel() < B * A:
+            raise RuntimeError(f"out: need >= {B * A} contiguous float32 on {self.device}")
+        N.check(self._lib.porl_qnet_bcq_mask(self._h, N.ptr(next_states), self.cfg.state_dim, N.ptr(idx), B, float(threshold),
+                                             N.ptr(out), N.current_stream_ptr(self.device)), "porl_qnet_bcq_mask")
+        return out
+
+    def bcq_learn_indexed(self, beh_engine, hp, states, actions, rewards, next_states, dones, idx, threshold):
+        """One BCQ step on rows `idx` of the replay arrays from one native call (porl_qnet_bcq_learn): behaviour mask of
+        `beh_engine`, masked-argmax step, Adam."""
+        self._ensure_bound()
+        beh_engine._ensure_bound()
+        B = idx.numel()
+        self._check_replay(states, actions, rewards, next_states, dones, 0, B, idx)
+        N.check(self._lib.porl_qnet_bcq_learn(
+            self._h, beh_engine._h, N.ptr(states), self.cfg.state_dim, N.ptr(actions), N.ptr(rewards), N.ptr(next_states),
+            self.cfg.state_dim, N.ptr(dones), N.ptr(idx), B, C.byref(hp), float(threshold),
+            N.current_stream_ptr(self.device)), "porl_qnet_bcq_learn")
+        self._stepped(hp)
+        return B
+
+    def bcq_learn_sampled(self, beh_engine, hp, states, actions, rewards, next_states, dones, n_rows, batch, seed, draw,
+                          threshold):
+        """bcq_learn_indexed on the rows engine.sample_indices(n_rows, batch, seed, draw) would give, drawn inside the
+        mask kernel and the step kernel (porl_qnet_bcq_learn_sampled); needs can_sample."""
+        self._ensure_bound()
+        beh_engine._ensure_bound()
+        self._check_replay(states, actions, rewards, next_states, dones, n_rows, batch)
+        N.check(self._lib.porl_qnet_bcq_learn_sampled(
+            self._h, beh_engine._h, N.ptr(states), self.cfg.state_dim, N.ptr(actions), N.ptr(rewards), N.ptr(next_states),
+            self.cfg.state_dim, N.ptr(dones), int(n_rows), int(seed), int(draw), int(batch), C.byref(hp), float(threshold),
+            N.current_stream_ptr(self.device)), "porl_qnet_bcq_learn_sampled")
+        self._stepped(hp)
+        return batch
+
     @property
     def can_sample(self):
         return bool(self._lib.porl_qnet_can_sample(self._h))

@@ -25,6 +25,9 @@ device-resident PrioritizedReplayBuffer, so
   * learn: sample_slots (one copy of the batch's uniforms, drawn from Python's `random` exactly as the reference draws
     them, one launch for tree walk, weights and their mean) -> the step kernel on rows `slots` (Double-DQN, importance
     weights or their mean, |TD| out) -> update_priorities_device (one launch); losses deferred as above.
+BCQ flavour (`_FastBCQ`, BCQTrainer.train_online(policy=bcq_learn)): the same ring and deferred loss around
+porl_qnet_bcq_learn — the behaviour mask computed from the replay rows by one kernel, then the step kernel with the
+masked bootstrap action, reduction and Adam, all from one native call.
 IQN flavour (`_FastIQN`, IQNTrainer; the reference's scripts/train_iqn.py drives exactly this loop): the network is not
 an MLP a QnetEngine covers, so the trainer's own IqnEngine (csrc/iqn_api.inc) stands in for it:
   * greedy action: the fractions are drawn as select_action draws them (torch.rand(1, N_policy) on the device), then
@@ -191,6 +194,15 @@ class _FastPER(_Fast):
         eng.learn_indexed(hp, *self.views, slots, variant=var)
         mem.update_priorities_device(tree_idx, td_abs)
         return self._deferred_loss()
+
+
+class _FastBCQ(_Fast):
+    """BCQTrainer with policy=bcq_learn: act and record as _Fast; learn = numpy's draw through the index ring into
+    policy.bcq.bcq_learn_rows' launch (porl_qnet_bcq_learn: behaviour mask from the rows, masked-argmax step, Adam)."""
+
+    def __init__(self, trainer):
+        from ..policy.bcq import _launch_rows
+        super().__init__(trainer, learn_rows=lambda idx: _launch_rows(trainer, idx))
 
 
 class _FastIQN(_Fast):
