@@ -618,6 +618,42 @@ int porl_epoch_indices(int64_t n_rows, int64_t first, int32_t count, uint64_t se
 int porl_state2costmap(float* state, int64_t state_rs, int32_t batch, int32_t n_ang, int32_t n_dist,
                        float* out, void* stream);
 
+/* The labelling pass between the CSV shards and the value dataset (preprocess.py:11-68 `preprocessing`, planner
+ * dataloader/a_star.py:8-221; CustomDataset.__init__ runs the same pass, dataloader/dataloader.py:18-30), one
+ * workgroup per row with the occupancy grid and the distance field in LDS (csrc/astar.hpp).  Per row: the n_beams
+ * ranges become obstacle points (beams with range_lo < d < range_hi, at beam_dirs[i] * d), the points block every
+ * cell whose centre (ix * resolution + min_x, iy * resolution + min_y) lies within robot_radius, and the row is
+ * labelled with the number of nodes on a cheapest 8-connected path from the cell of (0, 0) to the goal's cell,
+ * goal = R(heading) (row[goal_off .. +1] - row[pose_off .. +1]).  All geometry is fp64 on the fp32 row's values.
+ * The grid is round((max - min) / resolution) cells per axis; it is rejected (PORL_ERR_INVALID, before any launch)
+ * when its distance field does not fit in one workgroup's LDS or a path could overflow the packed (a, b) pair. */
+typedef struct porl_astar_params {
+  double resolution, robot_radius;            /* reference: 0.1, 0.13 (also the row filter's threshold) */
+  double min_x, max_x, min_y, max_y;          /* reference: -10, 10, -5, 5 */
+  double range_lo, range_hi;                  /* reference: 0.15, 3.5 (both exclusive) */
+  int32_t n_beams;                            /* reference: 360, at row[0 .. n_beams) */
+  int32_t pose_off, heading_off, goal_off;    /* reference: 360 (x, y), 362, 363 (x, y) */
+} porl_astar_params;
+
+enum {
+  PORL_ASTAR_LABELLED = 0,       /* value = value_table[path_len] */
+  PORL_ASTAR_TOO_CLOSE = 1,      /* min(scan) < robot_radius (numpy's min: false when a beam is NaN) */
+  PORL_ASTAR_GOAL_IS_START = 2,
+  PORL_ASTAR_GOAL_OFF_GRID = 3,
+  PORL_ASTAR_GOAL_BLOCKED = 4,
+  PORL_ASTAR_UNREACHABLE = 5,
+  PORL_ASTAR_NON_FINITE = 6,     /* the goal cell is not a finite number (the reference raises from round()) */
+  PORL_ASTAR_NOT_CONVERGED = 7   /* the sweep bound was reached: never expected, reported instead of spinning */
+};
+
+/* rows (n_rows, >= highest offset read) fp32 with `row_stride` floats between rows; beam_dirs (n_beams, 2) fp64
+ * (cos, sin) of each beam, built on the host; value_table[n] fp32 = the label of an n-node path, n_values >= cells + 2.
+ * Outputs, one per row: value (0 unless labelled), path_len (a + b + 1, or 0), status (above); `sweeps` (relaxation
+ * sweeps the row took) may be null.  The reference drops every row whose status is not 0. */
+int porl_astar_label(const float* rows, int64_t row_stride, int64_t n_rows, const porl_astar_params* params,
+                     const double* beam_dirs, const float* value_table, int32_t n_values, float* value,
+                     int32_t* path_len, int32_t* status, int32_t* sweeps, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Costmap encoder engine: FasterNet.forward_cls (agent/fasternet.py:428-438) as built by
  * sorl_train.py:29 `FasterNet(3, args.feature_dim)` — state2costmap, PatchEmbed 4x4s4 + BN (:234-246),

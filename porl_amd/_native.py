@@ -23,7 +23,7 @@ SYMBOLS = [
     "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_only_forward", "porl_iql_policy_only_step", "porl_iql_policy_prefetch", "porl_iql_forward_value", "porl_iql_forward_policy",
     "porl_gemm_f32", "porl_gemm_f32_group", "porl_adam_ema", "porl_ema", "porl_softmax_mask", "porl_gather_rows", "porl_sample_indices", "porl_epoch_indices", "porl_per_update", "porl_per_sample",
     "porl_per_record", "porl_per_sample_slots", "porl_per_update_f32",
-    "porl_prof_enable", "porl_prof_read", "porl_tune_set", "porl_tune_set_ptr", "porl_state2costmap",
+    "porl_prof_enable", "porl_prof_read", "porl_tune_set", "porl_tune_set_ptr", "porl_state2costmap", "porl_astar_label",
     "porl_signal_create", "porl_signal_destroy", "porl_signal_write", "porl_signal_wait_ge", "porl_iql_update_pipelined",
     "porl_qnet_create", "porl_qnet_destroy", "porl_qnet_param_floats", "porl_qnet_tensors",
     "porl_qnet_tensor_info", "porl_qnet_workspace_floats", "porl_qnet_bind", "porl_qnet_load_batch",
@@ -127,6 +127,12 @@ class EncCfg(C.Structure):
                [("mlp_ratio", C.c_float), ("bn_eps", C.c_float), ("bn_momentum", C.c_float), ("bf16_operands", C.c_int32)]
 
 
+class AstarParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("resolution", "robot_radius", "min_x", "max_x", "min_y", "max_y", "range_lo",
+                                          "range_hi")] + \
+               [(n, C.c_int32) for n in ("n_beams", "pose_off", "heading_off", "goal_off")]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double)]
@@ -188,6 +194,7 @@ def _declare(lib):
     lib.porl_iql_update_pipelined.argtypes = [vp, C.POINTER(IqlHyper), i32, vp, i64, i64, i32, i32, C.c_uint64, C.c_uint64,
                                               vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, i32, vp, vp]
     lib.porl_state2costmap.argtypes = [vp, i64, i32, i32, i32, vp, vp]
+    lib.porl_astar_label.argtypes = [vp, i64, i64, C.POINTER(AstarParams), vp, vp, i32, vp, vp, vp, vp, vp]
     lib.porl_qnet_create.argtypes = [C.POINTER(QnetCfg), C.POINTER(vp)]
     lib.porl_qnet_destroy.argtypes = [vp]
     lib.porl_qnet_destroy.restype = None

@@ -23,6 +23,7 @@
 #include "online.hpp"
 #include "per_online.hpp"
 #include "bcq_mask.hpp"
+#include "astar.hpp"
 
 using namespace porl;
 
@@ -1846,6 +1847,68 @@ int porl_state2costmap(float* state, int64_t state_rs, int32_t batch, int32_t n_
   const long n = (long)batch * (n_ang + 2);
   hipLaunchKernelGGL(clamp_gt8_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 1024)), dim3(256), 0, s, state,
                      (long)state_rs, n_ang + 2, batch);
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+// ---- dataset labelling (astar.hpp) ---------------------------------------------------------------------------------
+namespace {
+// Grid and launch constants of a parameter set; every rejection names its argument.  No HIP call.
+int astar_plan(const porl_astar_params& p, int64_t row_stride, int32_t n_values, AstarGrid* out) {
+  const double vals[] = {p.resolution, p.robot_radius, p.min_x, p.max_x, p.min_y, p.max_y, p.range_lo, p.range_hi};
+  for (double v : vals) if (!std::isfinite(v)) PORL_FAIL(PORL_ERR_INVALID, "params: every field must be finite");
+  if (!(p.resolution > 0.0)) PORL_FAIL(PORL_ERR_INVALID, "params.resolution %g must be positive", p.resolution);
+  if (p.robot_radius < 0.0) PORL_FAIL(PORL_ERR_INVALID, "params.robot_radius %g must not be negative", p.robot_radius);
+  if (!(p.max_x > p.min_x) || !(p.max_y > p.min_y)) PORL_FAIL(PORL_ERR_INVALID, "params: need min_x < max_x and min_y < max_y");
+  if (p.n_beams < 1) PORL_FAIL(PORL_ERR_INVALID, "params.n_beams %d must be positive", p.n_beams);
+  if (p.pose_off < 0 || p.heading_off < 0 || p.goal_off < 0) PORL_FAIL(PORL_ERR_INVALID, "params: negative row offset");
+  const int64_t need = std::max<int64_t>(std::max<int64_t>(p.n_beams, (int64_t)p.pose_off + 2),
+                                         std::max<int64_t>((int64_t)p.heading_off + 1, (int64_t)p.goal_off + 2));
+  if (row_stride < need)
+    PORL_FAIL(PORL_ERR_INVALID, "row_stride %lld shorter than the highest offset read (%lld floats)", (long long)row_stride,
+              (long long)need);
+  // cells per axis as the reference counts them: round() of the quotient, half to even (nearbyint in the default mode)
+  const double wd = std::nearbyint((p.max_x - p.min_x) / p.resolution), hd = std::nearbyint((p.max_y - p.min_y) / p.resolution);
+  if (wd < 1.0 || hd < 1.0) PORL_FAIL(PORL_ERR_INVALID, "params.resolution %g leaves no cell in the window", p.resolution);
+  const double pcd = (wd + 2.0) * (hd + 2.0);
+  if (wd * hd > (double)AS_MAX_PAIR || pcd > (double)AS_MAX_PADDED_CELLS || astar_lds_bytes((int64_t)pcd) > (size_t)AS_MAX_LDS_BYTES)
+    PORL_FAIL(PORL_ERR_INVALID, "params.resolution %g: a %.0f x %.0f grid does not fit one workgroup (%.0f bytes of LDS needed, "
+              "%d available; at most %d cells)", p.resolution, wd, hd, pcd * 4.0 + pcd / 8.0, AS_MAX_LDS_BYTES, AS_MAX_PAIR);
+  const double sx = std::nearbyint((0.0 - p.min_x) / p.resolution), sy = std::nearbyint((0.0 - p.min_y) / p.resolution);
+  if (sx < 0.0 || sx >= wd || sy < 0.0 || sy >= hd)
+    PORL_FAIL(PORL_ERR_INVALID, "params: the robot's cell (%.0f, %.0f) lies outside the %.0f x %.0f grid", sx, sy, wd, hd);
+  if ((double)n_values < wd * hd + 2.0)
+    PORL_FAIL(PORL_ERR_INVALID, "n_values %d: value_table must cover path lengths up to cells + 1 = %.0f", n_values, wd * hd + 1.0);
+  AstarGrid g;
+  g.res = p.resolution; g.rr = p.robot_radius; g.min_x = p.min_x; g.min_y = p.min_y; g.range_lo = p.range_lo; g.range_hi = p.range_hi;
+  g.w = (int32_t)wd; g.h = (int32_t)hd; g.pw = g.w + 2; g.pcells = (g.w + 2) * (g.h + 2);
+  g.start_ix = (int32_t)sx; g.start_iy = (int32_t)sy;
+  g.n_beams = p.n_beams; g.pose_off = p.pose_off; g.heading_off = p.heading_off; g.goal_off = p.goal_off;
+  g.max_sweeps = g.w * g.h;
+  *out = g;
+  return PORL_OK;
+}
+}  // namespace
+
+int porl_astar_label(const float* rows, int64_t row_stride, int64_t n_rows, const porl_astar_params* params,
+                     const double* beam_dirs, const float* value_table, int32_t n_values, float* value, int32_t* path_len,
+                     int32_t* status, int32_t* sweeps, void* stream) {
+  if (!rows) PORL_FAIL(PORL_ERR_INVALID, "null rows");
+  if (!params) PORL_FAIL(PORL_ERR_INVALID, "null params");
+  if (!beam_dirs) PORL_FAIL(PORL_ERR_INVALID, "null beam_dirs");
+  if (!value_table) PORL_FAIL(PORL_ERR_INVALID, "null value_table");
+  if (!value) PORL_FAIL(PORL_ERR_INVALID, "null value");
+  if (!path_len) PORL_FAIL(PORL_ERR_INVALID, "null path_len");
+  if (!status) PORL_FAIL(PORL_ERR_INVALID, "null status");
+  if (n_rows < 1 || n_rows >= (int64_t(1) << 31)) PORL_FAIL(PORL_ERR_INVALID, "n_rows %lld outside [1, 2^31)", (long long)n_rows);
+  AstarGrid g;
+  PORL_TRY(astar_plan(*params, row_stride, n_values, &g));
+  const size_t lds = astar_lds_bytes(g.pcells);
+  DevGuard _dg(device_of(status));
+  PORL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&astar_label_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds));
+  hipLaunchKernelGGL(astar_label_kernel, dim3((unsigned)n_rows), dim3(AS_THREADS), lds, (hipStream_t)stream, rows,
+                     (long)row_stride, g, beam_dirs, value_table, value, path_len, status, sweeps);
   PORL_HIP(hipGetLastError());
   return PORL_OK;
 }

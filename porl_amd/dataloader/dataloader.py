@@ -8,6 +8,8 @@ keeps CSV files of 100 such rows (dataloader.py:13: S=365, A=2 -> 734 floats).  
     pack_csv_dir(src_dir, out.npy, row_width)   CSV shards -> ONE packed fp32 row file (host, once)
     DeviceDataset(path_or_array, device)        memory-map the file and stream it to HBM in bounded chunks;
                                                 a rank of an N-GPU job keeps only rows shard_bounds(N, rank, world)
+    label_dataset(dataset)                      (astar.py) the A* value labels of the transition rows, on the device:
+                                                a DeviceDataset of `[scan | value]` records (preprocess.py:11-68)
     EpochLoader(dataset, batch_size)            `for data in loader:` yields (b, row_width) device tensors; an epoch is
                                                 one keyed permutation of the rows walked batch by batch (indices
                                                 drawn on the device, rows gathered by one kernel), the last batch
@@ -68,6 +70,23 @@ class DeviceDataset:
             b = min(n, a + chunk_rows)
             self.rows[a:b].copy_(torch.from_numpy(np.array(rows[self.lo + a:self.lo + b], dtype=np.float32)))   # a writable copy of the chunk
         self.rank, self.world = rank, world
+
+    @classmethod
+    def from_tensor(cls, rows, rank=0, world=1):
+        """Wrap (N, width) fp32 rows that are already on the device — the output of a device-side pass such as
+        `label_dataset` — without a round trip through the host.  The tensor is kept, not copied; it is this rank's
+        shard as it stands."""
+        if rows.device.type != "cuda":
+            raise E.N.NativeError("DeviceDataset keeps the rows on a HIP device (device='cuda'); there is no CPU path")
+        if rows.dim() != 2 or rows.dtype != torch.float32:
+            raise ValueError(f"expected (N, width) float32 rows, got {rows.dtype} {tuple(rows.shape)}")
+        self = cls.__new__(cls)
+        self.device = rows.device
+        self.rows = rows.contiguous()
+        self.n_total, self.width = int(rows.shape[0]), int(rows.shape[1])
+        self.lo, self.hi = 0, self.n_total
+        self.rank, self.world = rank, world
+        return self
 
     def __len__(self):
         return self.rows.shape[0]

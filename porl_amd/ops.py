@@ -5,7 +5,7 @@ The operators are a thin layer: tensors in, raw pointers + sizes + the current H
 handed to libporl_hip.so.  Engines (which own flat parameter groups, Adam state and workspace) are referred to by an
 integer handle obtained from `register_engine(obj)`; `por_step` / `iql_value_step` / `awr_policy_step` / `cql_step`
 are what the agent classes run per minibatch, `replay_gather` / `adam_ema_sweep` / `mlp_forward` / `gemm_f32` /
-`sample_indices` / `state2costmap` are the building blocks.
+`sample_indices` / `state2costmap` / `astar_label` are the building blocks.
 
 Only the CUDA (= HIP on ROCm) dispatch key has an implementation.  There is NO CPU kernel: calling an operator with
 CPU tensors raises `NativeError`, like every other entry of this package.
@@ -63,6 +63,10 @@ SCHEMAS = {
     "gemm_f32": "(Tensor a, Tensor b, Tensor? bias, int act) -> Tensor",
     "sample_indices": "(int n_rows, int batch, int seed, int step, Tensor like) -> Tensor",
     "state2costmap": "(Tensor(a!) state, int angle_bins, int dist_bins) -> Tensor",
+    # A* path-value labels of transition rows (preprocess.py:11-68) -> (value, path_len, status) per row
+    "astar_label": "(Tensor rows, float resolution=0.1, float robot_radius=0.13, float min_x=-10., float max_x=10., "
+                   "float min_y=-5., float max_y=5., float range_lo=0.15, float range_hi=3.5, int n_beams=360, "
+                   "int pose_offset=360, int heading_offset=362, int goal_offset=363) -> (Tensor, Tensor, Tensor)",
 }
 for _name, _schema in SCHEMAS.items():
     LIB.define(_name + _schema)
@@ -160,9 +164,18 @@ def _state2costmap(state, angle_bins, dist_bins):
     return state2costmap(state, angle_bins, dist_bins)
 
 
+def _astar_label(rows, resolution=0.1, robot_radius=0.13, min_x=-10., max_x=10., min_y=-5., max_y=5., range_lo=0.15,
+                 range_hi=3.5, n_beams=360, pose_offset=360, heading_offset=362, goal_offset=363):
+    # the defaults are the schema's: a Python kernel is handed the caller's arguments, not the schema's defaults
+    from .dataloader.astar import astar_values
+    return astar_values(rows, resolution=resolution, robot_radius=robot_radius, min_x=min_x, max_x=max_x, min_y=min_y,
+                        max_y=max_y, range_lo=range_lo, range_hi=range_hi, n_beams=n_beams, pose_offset=pose_offset,
+                        heading_offset=heading_offset, goal_offset=goal_offset)
+
+
 _IMPLS = dict(por_step=_por_step, iql_value_step=_iql_value_step, awr_policy_step=_awr_policy_step, cql_step=_cql_step,
               replay_gather=_replay_gather, adam_ema_sweep=_adam_ema_sweep, mlp_forward=_mlp_forward, gemm_f32=_gemm_f32,
-              sample_indices=_sample_indices, state2costmap=_state2costmap)
+              sample_indices=_sample_indices, state2costmap=_state2costmap, astar_label=_astar_label)
 
 
 def _no_cpu(name):
