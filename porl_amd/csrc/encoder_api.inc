@@ -184,12 +184,7 @@ template <int CP, int OCB, int WW>
 int enc_pconv_launch(const float* x, const float* w, float* y, int batch, int Hh, int C, hipStream_t s) {
   constexpr int TR = 64 / (WW / 4);
   const size_t lds = (size_t)((TR + 2) * CP * (WW + 8)) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    PORL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pconv3x3_kernel<CP, OCB, WW>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  PORL_TRY((dyn_lds_once<&pconv3x3_kernel<CP, OCB, WW>>((int)lds)));
   ProfScope ps("pconv3x3_kernel", s, 2.0 * batch * Hh * WW * 9.0 * CP * CP, 8.0 * batch * Hh * WW * C);
   hipLaunchKernelGGL((pconv3x3_kernel<CP, OCB, WW>), dim3(cdiv(Hh, TR), batch, CP / OCB), dim3(64 * (OCB / 8)), lds, s, x,
                      w, y, Hh, C);
@@ -306,12 +301,8 @@ int enc_mlp_bf16_launch(porl_enc* h, const EncBlock& b, __bf16* x, const __bf16*
   const long ntiles = (rows + 127) / 128;
   const unsigned grid = (unsigned)ntiles;                          // one 128-row tile per block (see PFA in the kernel)
   constexpr int LDS1 = enc_mlp_lds_bytes<DIM, HID, CP>(1), LDS2 = enc_mlp_lds_bytes<DIM, HID, CP>(2);
-  static bool attr = false;
-  if (!attr) {
-    PORL_TRY(enc_set_lds(&enc_mlp_bf16_kernel<DIM, HID, CP, 1>, LDS1));
-    PORL_TRY(enc_set_lds(&enc_mlp_bf16_kernel<DIM, HID, CP, 2>, LDS2));
-    attr = true;
-  }
+  PORL_TRY((dyn_lds_once<&enc_mlp_bf16_kernel<DIM, HID, CP, 1>>(LDS1)));
+  PORL_TRY((dyn_lds_once<&enc_mlp_bf16_kernel<DIM, HID, CP, 2>>(LDS2)));
   if (training) {
     {
       ProfScope ps("enc_mlp_bf16_kernel<stats>", s, 2.0 * rows * DIM * HID, 2.0 * rows * DIM);
@@ -617,8 +608,7 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
       a.cstat = training ? W + h->ws_cstat : nullptr;
       a.Hp = h->Hp; a.Wp = h->Wp; a.H2 = h->H2; a.W2 = h->W2; a.rows2 = rows2;
       constexpr int MLDS = 2 * (64 * (4 * 96 + 8) + 192 * (96 + 8));
-      static bool attr = false;
-      if (!attr) { PORL_TRY(enc_set_lds(&enc_merge_bf16_kernel<96>, MLDS)); attr = true; }
+      PORL_TRY(dyn_lds_once<&enc_merge_bf16_kernel<96>>(MLDS));
       ProfScope ps("enc_merge_bf16_kernel", s, 2.0 * rows2 * 4.0 * E * E2, 2.0 * rows2 * (4.0 * E + E2));
       hipLaunchKernelGGL(enc_merge_bf16_kernel<96>, dim3((unsigned)((rows2 + 63) / 64)), dim3(256), MLDS, s, a);
       PORL_HIP(hipGetLastError());

@@ -335,12 +335,8 @@ int porl_iqn_act(porl_iqn* h, int which, const porl_qnet_act_src* src, const flo
   }
   const int vec = H % 4 == 0 && aligned16(P + c.offset[IQN_V1W]) && aligned16(hv);        // (Hp == H then: both row strides are multiples of 4)
   IqnActHeadArgs a{hv, (long)Hp, P + c.offset[IQN_V1W], (long)H, P + c.offset[IQN_V1B], h->buf.stats, n_stats, h->act_out_dev, n_tau, H, A, vec};
-  static bool attr_set = false;                  // up to 256 x 64 floats of dynamic LDS beside the kernel's static 256 bytes
-  if (!attr_set) {
-    PORL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&iqn_act_head_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)sizeof(float) * IQN_MAX_TAU * IQN_MAX_A));
-    attr_set = true;
-  }
+  // up to 256 x 64 floats of dynamic LDS beside the kernel's static 256 bytes
+  PORL_TRY(dyn_lds_once<&iqn_act_head_kernel>((int)sizeof(float) * IQN_MAX_TAU * IQN_MAX_A));
   hipLaunchKernelGGL(iqn_act_head_kernel, dim3(1), dim3(n_tau >= 16 ? 1024 : 256), sizeof(float) * n_tau * A, s, a);
   PORL_HIP(hipGetLastError());
   return PORL_OK;

@@ -2,7 +2,7 @@
 // 60 -> 64 -> 128 -> 64 -> 10 at batch 4096).  Every layer is at most 128 wide, so a block keeps 32 minibatch
 // rows, one layer's weights and all activations of those rows in LDS and walks the whole step itself:
 //   target net on s' -> online net on s -> TD target, logsumexp penalty, dL/dQ -> backward through the layers.
-// The multi-launch path (porl_api.hip) spends ~7 us per dependent launch on ~20 launches of a few us each; this
+// The multi-launch path (qnet_api.inc) spends ~7 us per dependent launch on ~20 launches of a few us each; this
 // kernel is latency-bound inside one block instead.  Matrix work runs on v_mfma_f32_32x32x2_f32 (exact fp32
 // fmaf chains): forward and dgrad tiles are 32 rows x 32 columns per wave, wgrad tiles 32 x 32 of dW per wave
 // with the 32 rows as the reduction.  Per-block partial gradients go to a slab in the flat parameter layout
