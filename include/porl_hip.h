@@ -105,6 +105,18 @@ int porl_iql_load_batch_sampled(porl_iql* h, int32_t batch, const float* rows, i
                                 int64_t n_rows, int32_t act_dim, int32_t target_is_action,
                                 uint64_t seed, uint64_t step, int64_t* idx_out, void* stream);
 
+/* porl_iql_load_batch for rows idx[0..batch) of a packed store [s(state_dim) | r | s'(state_dim) | d | a(act_dim)]:
+ * r, d and the policy target (s' if !target_is_action, else the action columns) come from the rows; observations
+ * and next observations come from obs_feat / next_feat (batch, cfg.obs_dim) when given (encoder features), or from
+ * the rows themselves when both are NULL (then state_dim must equal cfg.obs_dim).  clamp_target_gt8: stage target
+ * values > 8 as 0 (POR with a backbone regresses the next state as the encoder's clamp leaves it, por.py:75-79).
+ * Honours PORL_IQL_MODE_TWO_SLOTS and resets the same per-batch flags as porl_iql_load_batch_sampled.  The store is
+ * only read.  Contract for idx as porl_gather_rows: 0 <= idx[b] < n_rows is the caller's; duplicates are allowed. */
+int porl_iql_load_batch_indexed(porl_iql* h, int32_t batch, const float* rows, int64_t row_stride, int64_t n_rows,
+                                const int64_t* idx, int32_t state_dim, int32_t act_dim, int32_t target_is_action,
+                                int32_t clamp_target_gt8, const float* obs_feat, int64_t obs_rs,
+                                const float* next_feat, int64_t next_rs, void* stream);
+
 /* Execution mode of the phase calls (default 0).
  *   PORL_IQL_MODE_TWO_SLOTS   : the minibatch staging buffers the policy phase reads (s, policy target, TD target)
  *       exist PORL_IQL_SLOTS times and every porl_iql_load_batch* call moves to the next copy.  The policy phase of
@@ -722,6 +734,14 @@ int porl_enc_weights_changed(porl_enc* h);
  * sample (fasternet.py:76-93) or NULL for none; features (batch, num_classes), row stride feat_rs. */
 int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch, int32_t training,
                      const float* drop_scale, float* features, int64_t feat_rs, void* stream);
+/* porl_enc_forward on rows of a resident packed store, read in place: sample b is the n_ang + 2 floats at
+ * rows + idx[b] * row_stride + col_offset.  The store is NOT modified: values > 8 are read as 0 (what the
+ * reference's in-place clamp, util/costmap.py:17, would leave), nothing is written back.  Everything after the
+ * patch embedding is porl_enc_forward's code.  Contract for idx as porl_gather_rows: 0 <= idx[b] < n_rows is the
+ * caller's. */
+int porl_enc_forward_rows(porl_enc* h, const float* rows, int64_t row_stride, int64_t n_rows, const int64_t* idx,
+                          int32_t col_offset, int32_t batch, int32_t training, const float* drop_scale,
+                          float* features, int64_t feat_rs, void* stream);
 
 /* Prioritized replay on the device (src/porl/buffer/sum_tree.py:4-77, prioritized_replay_buffer.py:36-108).
  * `tree`: 2*capacity-1 doubles in the reference's heap layout (leaf of data slot d at d + capacity - 1).

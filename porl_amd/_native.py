@@ -18,7 +18,7 @@ SYMBOLS = [
     "porl_abi_version", "porl_last_error",
     "porl_iql_create", "porl_iql_destroy", "porl_iql_group_floats", "porl_iql_group_tensors",
     "porl_iql_tensor_info", "porl_iql_workspace_floats", "porl_iql_bind", "porl_iql_load_batch",
-    "porl_iql_load_batch_sampled", "porl_iql_set_stats", "porl_iql_set_mode", "porl_iql_tune_set",
+    "porl_iql_load_batch_sampled", "porl_iql_load_batch_indexed", "porl_iql_set_stats", "porl_iql_set_mode", "porl_iql_tune_set",
     "porl_iql_value_backward", "porl_iql_value_apply", "porl_iql_policy_forward", "porl_iql_policy_backward",
     "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_only_forward", "porl_iql_policy_only_step", "porl_iql_policy_prefetch", "porl_iql_forward_value", "porl_iql_forward_policy",
     "porl_gemm_f32", "porl_gemm_f32_group", "porl_adam_ema", "porl_ema", "porl_softmax_mask", "porl_gather_rows", "porl_sample_indices", "porl_epoch_indices", "porl_per_update", "porl_per_sample",
@@ -35,7 +35,7 @@ SYMBOLS = [
     "porl_iqn_mix", "porl_iqn_head",
     "porl_enc_create", "porl_enc_destroy", "porl_enc_param_floats", "porl_enc_stat_floats",
     "porl_enc_workspace_floats", "porl_enc_tensors", "porl_enc_norms", "porl_enc_blocks",
-    "porl_enc_tensor_info", "porl_enc_norm_info", "porl_enc_bind", "porl_enc_weights_changed", "porl_enc_forward",
+    "porl_enc_tensor_info", "porl_enc_norm_info", "porl_enc_bind", "porl_enc_weights_changed", "porl_enc_forward", "porl_enc_forward_rows",
     "porl_enc_tap_info",
 ]
 
@@ -162,6 +162,7 @@ def _declare(lib):
     lib.porl_iql_bind.argtypes = [vp, C.POINTER(IqlBuffers)]
     lib.porl_iql_load_batch.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     lib.porl_iql_load_batch_sampled.argtypes = [vp, i32, vp, i64, i64, i32, i32, C.c_uint64, C.c_uint64, vp, vp]
+    lib.porl_iql_load_batch_indexed.argtypes = [vp, i32, vp, i64, i64, vp, i32, i32, i32, i32, vp, i64, vp, i64, vp]
     lib.porl_iql_set_stats.argtypes = [vp, vp]
     lib.porl_iql_set_mode.argtypes = [vp, i32]
     for name in ("porl_iql_value_backward", "porl_iql_value_apply", "porl_iql_policy_forward", "porl_iql_policy_backward",
@@ -271,6 +272,7 @@ def _declare(lib):
     lib.porl_enc_bind.argtypes = [vp, vp, vp, vp]
     lib.porl_enc_weights_changed.argtypes = [vp]
     lib.porl_enc_forward.argtypes = [vp, vp, i64, i32, i32, vp, vp, i64, vp]
+    lib.porl_enc_forward_rows.argtypes = [vp, vp, i64, i64, vp, i32, i32, i32, vp, vp, i64, vp]
     lib.porl_prof_enable.argtypes = [C.c_int]
     lib.porl_prof_read.argtypes = [C.POINTER(ProfEntry), C.c_int]
     for name in SYMBOLS:

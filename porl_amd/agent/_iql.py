@@ -9,6 +9,7 @@ import warnings
 import torch
 import torch.nn as nn
 
+from ..buffer.replay_buffer import PackedReplay
 from ..engine import IqlEngine
 from ..parallel import GradExchange
 
@@ -214,7 +215,8 @@ class IqlAgentBase(nn.Module):
             adam_beta1=v_opt.param_groups[0]["betas"][0], adam_beta2=v_opt.param_groups[0]["betas"][1],
             adam_eps=v_opt.param_groups[0]["eps"])
 
-    def _full_update(self, obs, next_obs, rew, term, pol_target, v_opt, p_opt, sched, replay=None, batch=None):
+    def _full_update(self, obs, next_obs, rew, term, pol_target, v_opt, p_opt, sched, replay=None, batch=None, idx=None,
+                     feats=None):
         """One update = value phase (load, forward, backward, [exchange], Adam + target EMA) then policy phase
         (second twin forward, weights, NLL, backward, [exchange], Adam), reference por.py:81-110.
 
@@ -226,6 +228,8 @@ class IqlAgentBase(nn.Module):
         Same arithmetic, same results; `flush()` (called by everything that reads the agent) joins the streams.  The
         returned statistics view is complete only after `flush()` (or a device synchronisation): g_loss and min NLL of
         the last update are written by the side stream.
+        Rows given by index (`idx`, with a backbone their features `feats`) take the phase calls below, not the
+        one-call form, which draws raw rows itself.
         With a data-parallel group the two gradient exchanges ride on their phase's stream, so the policy-group
         all-reduce and most of the value-group one overlap with the other phase's kernels."""
         eng, ex = self._engine, self._exchange
@@ -240,7 +244,7 @@ class IqlAgentBase(nn.Module):
         use_sig = pipelined and _PIPE_SYNC in ("signal", "signal2") and eng.signals() is not None
         onecall = _PIPE_ONECALL is True or _PIPE_ONECALL == "1" or (
             _PIPE_ONECALL == "auto" and (batch or 0) * eng.cfg.hidden_dim ** 2 <= _ONECALL_MAX_WORK)
-        if use_sig and not dp and replay is not None and onecall:
+        if use_sig and not dp and replay is not None and idx is None and onecall:
             # the whole update from one native call (csrc: porl_iql_update_pipelined): the same operations on the same
             # two streams in the same order as the phase calls below, without ~12 trips through ctypes per update
             eng._seq += 1
@@ -278,12 +282,7 @@ class IqlAgentBase(nn.Module):
                 eng.wait_signal(eng.SIG_POLICY, seq - eng.SLOTS, main)
         elif pipelined:
             eng.wait_slot_free()               # the policy phase SLOTS updates ago used the staging slot loaded next
-        if replay is not None:
-            B = eng.load_batch_sampled(replay.rows, batch, replay.seed, replay.draws, replay.act_dim,
-                                       self._engine.cfg.weight_mode == 1)
-            replay.draws += 1
-        else:
-            B = eng.load_batch(obs, next_obs, rew, term, pol_target)
+        B = self._load(obs, next_obs, rew, term, pol_target, replay, batch, idx, feats)
         v_opt.step_count += 1
         p_opt.step_count += 1
         hp = self._hyper(B, v_opt, p_opt)
@@ -410,22 +409,62 @@ class IqlAgentBase(nn.Module):
         self.flush()
         return super().load_state_dict(*args, **kwargs)
 
-    def _load(self, obs, next_obs, rew, term, pol_target, replay, batch):
-        """Stage the minibatch: the given tensors, or `batch` rows drawn on the device from `replay` (PackedReplay)."""
+    def _replay_rows(self, replay, batch_size, indices):
+        """The rows of `replay` (PackedReplay) one *_from_replay call works on -> (idx, feats), both None for the draw that
+        the load kernel makes itself (no backbone, no `indices`: porl_iql_load_batch_sampled).
+        `indices`: an int64 device tensor of `batch_size` local row numbers to use instead of drawing (`replay.draws` does
+        not advance; range is the caller's contract, as for `PackedReplay.gather`; nothing here synchronises).
+        With a backbone the rows are drawn by `replay.sample_indices` (one draw) unless given, and s, then s' — the order
+        in which `update` consumes DropPath factors — are encoded where they lie in the store (`forward_rows`); the
+        store is only read.  Every check is made before anything is launched or counted."""
+        eng = self._engine
+        backbone = getattr(self, "backbone", None)
+        if backbone is not None and not isinstance(replay, PackedReplay):
+            raise NotImplementedError("with a backbone the rows are encoded in place in a PackedReplay; for any other "
+                                      "store, gather the rows and call the tensor form of the update")
+        raw = eng.cfg.obs_dim if backbone is None else backbone.ANGLE_BINS + 2
+        if replay.obs_dim != raw:
+            raise ValueError(f"replay rows carry {replay.obs_dim}-wide states, the agent takes {raw}-wide ones")
+        if indices is None and backbone is None:
+            return None, None
+        if indices is not None:
+            if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64:
+                raise RuntimeError(f"indices: expected an int64 tensor, got {getattr(indices, 'dtype', type(indices))}")
+            if tuple(indices.shape) != (batch_size,):
+                raise RuntimeError(f"indices: expected shape ({batch_size},), got {tuple(indices.shape)}")
+            if indices.device != eng.device:
+                raise RuntimeError(f"indices on {indices.device}, engine on {eng.device}")
+        limit = eng.cfg.max_batch if backbone is None else min(eng.cfg.max_batch, backbone._cfg.max_batch)
+        if not 1 <= batch_size <= limit:
+            raise RuntimeError(f"batch {batch_size} outside [1, {limit}] (max_batch)")
+        idx = replay.sample_indices(batch_size) if indices is None else indices.contiguous()
+        if backbone is None:
+            return idx, None
+        feats = (backbone.forward_rows(replay.rows, idx, 0), backbone.forward_rows(replay.rows, idx, replay.obs_dim + 1))
+        return idx, feats
+
+    def _load(self, obs, next_obs, rew, term, pol_target, replay, batch, idx=None, feats=None):
+        """Stage the minibatch: the given tensors, `batch` rows drawn on the device from `replay` (PackedReplay), or its
+        rows `idx` with their encoder features `feats` (`_replay_rows`)."""
         eng = self._engine
         if replay is None:
             return eng.load_batch(obs, next_obs, rew, term, pol_target)
-        B = eng.load_batch_sampled(replay.rows, batch, replay.seed, replay.draws, replay.act_dim,
-                                   eng.cfg.weight_mode == 1)
+        target_is_action = eng.cfg.weight_mode == 1
+        if idx is not None:
+            f_s, f_n = feats if feats is not None else (None, None)
+            # POR with a backbone regresses s' as the encoder's in-place clamp leaves it (por.py:75-79)
+            return eng.load_batch_indexed(replay.rows, idx, replay.obs_dim, replay.act_dim, target_is_action, f_s, f_n,
+                                          clamp_target_gt8=feats is not None and not target_is_action)
+        B = eng.load_batch_sampled(replay.rows, batch, replay.seed, replay.draws, replay.act_dim, target_is_action)
         replay.draws += 1
         return B
 
-    def _value_update(self, obs, next_obs, rew, term, v_opt, replay=None, batch=None):
+    def _value_update(self, obs, next_obs, rew, term, v_opt, replay=None, batch=None, idx=None, feats=None):
         eng, ex = self._engine, self._exchange
         eng.join()
         eng._ensure_bound()
         eng.set_mode(IqlEngine.MODE_FOLD_COMBINE if not ex.active else 0)
-        B = self._load(obs, next_obs, rew, term, None, replay, batch)
+        B = self._load(obs, next_obs, rew, term, None, replay, batch, idx, feats)
         v_opt.step_count += 1
         hp = self._hyper(B, v_opt, v_opt)
         eng.value_backward(hp)
@@ -441,7 +480,8 @@ class IqlAgentBase(nn.Module):
             ex.allreduce_stats_(eng.stats)
         eng.value_apply(hp)
 
-    def _policy_update(self, obs, next_obs, rew, term, pol_target, p_opt, sched, replay=None, batch=None):
+    def _policy_update(self, obs, next_obs, rew, term, pol_target, p_opt, sched, replay=None, batch=None, idx=None,
+                       feats=None):
         """Policy step with the value nets frozen (reference sorl.py:154-176; sibling of `_value_update`): TD target from
         the target twin, advantage from the online twin, weighted NLL, backward, Adam on the policy group only.  The
         value optimizer's step count and moments, the value nets and the target nets do not move; stats[0] keeps the
@@ -450,7 +490,7 @@ class IqlAgentBase(nn.Module):
         eng.join()                             # a pipelined update may still have its policy phase on the side stream
         eng._ensure_bound()
         eng.set_mode(IqlEngine.MODE_FOLD_COMBINE if not ex.active else 0)
-        B = self._load(obs, next_obs, rew, term, pol_target, replay, batch)
+        B = self._load(obs, next_obs, rew, term, pol_target, replay, batch, idx, feats)
         p_opt.step_count += 1
         hp = self._hyper(B, p_opt, p_opt)      # (value_lr / value_step are not read by the policy-only step)
         try:

@@ -16,7 +16,7 @@ Train mode (the reference never calls `.eval()`): BatchNorm normalises with batc
 running ones; DropPath (fasternet.py:76-93) draws one Bernoulli keep flag per sample and block.  The flags
 are drawn on the HOST from torch's default CPU generator, in the reference's order, so a CPU reference with
 the same seed sees the same masks.  Like the reference, `forward` zeroes entries > 8 of its input in place
-(util/costmap.py:17).
+(util/costmap.py:17); `forward_rows` encodes rows of a resident replay store where they lie and only reads them.
 """
 from __future__ import annotations
 
@@ -285,6 +285,45 @@ class FasterNet(nn.Module):
         return out
 
     forward_cls = forward
+
+    def forward_rows(self, rows, idx, col_offset=0, drop_scale=None):
+        """`forward` on rows of a resident packed store, read in place: sample b is the ANGLE_BINS + 2 floats of row
+        `idx[b]` of `rows` (2-D fp32 on the device, unit column stride) starting at column `col_offset`.  `idx` is an int64
+        tensor on the encoder's device; 0 <= idx[b] < len(rows) is the caller's contract, as for `PackedReplay.gather`.
+        `rows` is left untouched: entries > 8 are READ as 0, which is what `forward`'s in-place clamp would leave, so the
+        features equal `forward(rows[idx, col_offset:col_offset + ANGLE_BINS + 2].clone())` bit for bit.  DropPath
+        factors are drawn and `num_batches_tracked` advances exactly as in `forward`."""
+        self._ensure_bound()
+        w = self.ANGLE_BINS + 2
+        if rows.dim() != 2 or col_offset < 0 or col_offset + w > rows.shape[1]:
+            raise RuntimeError(f"rows: expected (n, >= col_offset + {w}) with col_offset >= 0, got {tuple(rows.shape)} "
+                               f"and col_offset {col_offset}")
+        if rows.dtype != torch.float32 or rows.stride(1) != 1:
+            raise RuntimeError("rows must be fp32 with unit column stride")
+        if _norm_device(rows.device) != self._device:
+            raise RuntimeError(f"rows are on {rows.device}, the encoder on {self._device}")
+        if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous():
+            raise RuntimeError(f"idx: expected a contiguous 1-D int64 tensor, got {idx.dtype} {tuple(idx.shape)}")
+        if _norm_device(idx.device) != self._device:
+            raise RuntimeError(f"idx is on {idx.device}, the encoder on {self._device}")
+        b = idx.numel()
+        if b < 1 or b > self._cfg.max_batch:
+            raise RuntimeError(f"batch {b} outside 1..max_batch {self._cfg.max_batch} the workspace was sized for")
+        if rows.shape[0] < 1:
+            raise RuntimeError("rows is empty")
+        if drop_scale is None:
+            drop_scale = self.draw_drop_scale(b)
+        if drop_scale is not None:
+            drop_scale = drop_scale.to(device=self._device, dtype=torch.float32).contiguous()
+            if tuple(drop_scale.shape) != (len(self._drop_probs), b):
+                raise RuntimeError(f"drop_scale: expected {(len(self._drop_probs), b)}, got {tuple(drop_scale.shape)}")
+        out = torch.empty(b, self.num_classes, dtype=torch.float32, device=self._device)
+        N.check(self._lib.porl_enc_forward_rows(self._h, N.ptr(rows), rows.stride(0), rows.shape[0], N.ptr(idx),
+                                                int(col_offset), b, int(self.training), N.ptr(drop_scale), N.ptr(out),
+                                                out.stride(0), N.current_stream_ptr(self._device)), "porl_enc_forward_rows")
+        if self.training:
+            torch._foreach_add_(self._nbt, 1)
+        return out
 
     TAP_NAMES = ("stages.0", "stages.2", "pooled", "avgpool_pre_head")
 

@@ -13,6 +13,9 @@ Deliberate differences from the reference (SURVEY.md §8 notes 6):
   * dead upstream code (`pretrain*`, `por_qlearning_update`, `save/load`) is not provided;
   * with `backbone=FasterNet(...)` (por.py:46-57,75-79) the encoder runs forward-only: it joins no optimizer
     upstream, so its backward only fills gradients nobody reads.
+
+Extension: `update_from_replay(replay, batch_size, indices=None)` runs the same step on rows of a device-resident
+`PackedReplay`, drawn on the device or named by `indices`, with or without a backbone; the store is only read.
 """
 from __future__ import annotations
 
@@ -68,12 +71,15 @@ class POR(IqlAgentBase):
         return agent._full_update(observations, next_observations, rewards, terminals, target,
                                   agent.v_optimizer, agent.goal_policy_optimizer, agent.goal_lr_schedule)
 
-    def update_from_replay(agent, replay, batch_size):
+    def update_from_replay(agent, replay, batch_size, indices=None):
         """Extension (not in the reference): one POR step on `batch_size` distinct rows drawn on the device
         from a `porl_amd.buffer.replay_buffer.PackedReplay` — sampling, gather and the update without any
-        host-side tensor work.  Same arithmetic as `por_residual_update` on those rows."""
-        if agent.backbone is not None:
-            raise NotImplementedError("update_from_replay draws packed [s | r | s' | d | a] rows for the heads; with a "
-                                      "backbone, gather the rows and call por_residual_update")
+        host-side tensor work.  Same arithmetic as `por_residual_update` on those rows, bit for bit.
+        `indices` (int64 device tensor of `batch_size` local row numbers) names the rows instead of drawing them; the
+        replay's draw counter then stays put.  With a backbone, s then s' are encoded where they lie in the store
+        (`FasterNet.forward_rows`): the store is never modified, entries > 8 are read as 0 by the encoder and staged as 0
+        in the regression target, which is what the in-place clamp of the tensor path leaves.  Raises ValueError when the
+        replay's state width is not the agent's."""
+        idx, feats = agent._replay_rows(replay, batch_size, indices)
         return agent._full_update(None, None, None, None, None, agent.v_optimizer, agent.goal_policy_optimizer,
-                                  agent.goal_lr_schedule, replay=replay, batch=batch_size)
+                                  agent.goal_lr_schedule, replay=replay, batch=batch_size, idx=idx, feats=feats)

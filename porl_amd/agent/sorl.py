@@ -12,7 +12,9 @@ taken from `update` / `vf_update` of the same file (sorl.py:85-89), `next_v = v_
 `target_v = r + (1 - d) * discount * next_v`; everything else is the method as written.  It runs as a step of its own
 on the device (five forward-only nets per layer in one launch, one head kernel for target, advantage and weight, the
 policy's backward and Adam) and leaves the value nets, the target nets and the value optimizer untouched.
-`vf_update_from_replay` / `policy_update_from_replay` are the two phases on rows drawn on the device.
+`vf_update_from_replay` / `policy_update_from_replay` are the two phases on rows drawn on the device; like
+`update_from_replay` they work with a backbone (rows encoded in place in the store).  `update_from_replay` also takes
+`indices=` to name the rows instead of drawing them.
 """
 from __future__ import annotations
 
@@ -94,19 +96,28 @@ class SORL(IqlAgentBase):
         return agent._policy_loss()
 
     def vf_update_from_replay(agent, replay, batch_size):
-        """Extension (not in the reference): `vf_update` on rows drawn on the device from a PackedReplay."""
-        agent._value_update(None, None, None, None, agent.v_optimizer, replay=replay, batch=batch_size)
+        """Extension (not in the reference): `vf_update` on rows drawn on the device from a PackedReplay; with a backbone
+        the rows are encoded where they lie in the store (see `update_from_replay`)."""
+        idx, feats = agent._replay_rows(replay, batch_size, None)
+        agent._value_update(None, None, None, None, agent.v_optimizer, replay=replay, batch=batch_size, idx=idx, feats=feats)
         if agent.async_losses:
             return agent._engine.stats[:1]
         return float(agent._engine.stats[0])
 
     def policy_update_from_replay(agent, replay, batch_size):
-        """Extension (not in the reference): `policy_update` on rows drawn on the device from a PackedReplay."""
+        """Extension (not in the reference): `policy_update` on rows drawn on the device from a PackedReplay; with a
+        backbone the rows are encoded where they lie in the store (see `update_from_replay`)."""
+        idx, feats = agent._replay_rows(replay, batch_size, None)
         agent._policy_update(None, None, None, None, None, agent.policy_optimizer, agent.lr_schedule,
-                             replay=replay, batch=batch_size)
+                             replay=replay, batch=batch_size, idx=idx, feats=feats)
         return agent._policy_loss()
 
-    def update_from_replay(agent, replay, batch_size):
-        """Extension (not in the reference): `update` on rows drawn on the device from a PackedReplay."""
+    def update_from_replay(agent, replay, batch_size, indices=None):
+        """Extension (not in the reference): `update` on `batch_size` rows of a PackedReplay — drawn on the device, or the
+        local row numbers in `indices` (int64 device tensor; the replay's draw counter then stays put).  Same arithmetic
+        as `update` on those rows, bit for bit.  With a backbone, s then s' are encoded where they lie in the store
+        (`FasterNet.forward_rows`), which is only read.  Raises ValueError when the replay's state width is not the
+        agent's."""
+        idx, feats = agent._replay_rows(replay, batch_size, indices)
         return agent._full_update(None, None, None, None, None, agent.v_optimizer, agent.policy_optimizer,
-                                  agent.lr_schedule, replay=replay, batch=batch_size)
+                                  agent.lr_schedule, replay=replay, batch=batch_size, idx=idx, feats=feats)

@@ -66,28 +66,33 @@ def build(force=False, verbose=True):
 SAN_OUT = os.path.join(HERE, "lib", "libporl_hip_host_san.so")
 SAN_DRIVER_SRC = os.path.join(os.path.dirname(HERE), "tests", "helpers", "abi_reject.cpp")
 SAN_DRIVER = os.path.join(HERE, "lib", "abi_reject_san")
+# second driver, same library: the entry points that read a packed replay store in place (tests/test_enc_replay_host.py)
+SAN_ROWS_DRIVER_SRC = os.path.join(os.path.dirname(HERE), "tests", "helpers", "abi_reject_rows.cpp")
+SAN_ROWS_DRIVER = os.path.join(HERE, "lib", "abi_reject_rows_san")
 SAN_FLAGS = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 
 def build_sanitized(force=False, verbose=True):
     """The same translation unit with AddressSanitizer + UBSan on the HOST half (planner, validation, layout code; the
-    device half is compiled as usual and never runs), plus the driver that walks the rejected-argument paths
-    (tests/helpers/abi_reject.cpp).  CPU-only check: GPU sanitizers are not available on this pool.  Returns the
-    driver's path; cached by source hash like the product library."""
+    device half is compiled as usual and never runs), plus the drivers that walk the rejected-argument paths
+    (tests/helpers/abi_reject.cpp -> SAN_DRIVER, tests/helpers/abi_reject_rows.cpp -> SAN_ROWS_DRIVER).  CPU-only check:
+    GPU sanitizers are not available on this pool.  Returns SAN_DRIVER; cached by source hash like the product
+    library."""
     import hashlib
-    h = hashlib.sha256((source_hash() + open(SAN_DRIVER_SRC).read()).encode()).hexdigest()
+    h = hashlib.sha256((source_hash() + open(SAN_DRIVER_SRC).read() + open(SAN_ROWS_DRIVER_SRC).read()).encode()).hexdigest()
     tag = SAN_OUT + ".srchash"
     try:
-        if not force and os.path.exists(SAN_OUT) and os.path.exists(SAN_DRIVER) and open(tag).read().strip() == h:
+        if not force and all(os.path.exists(f) for f in (SAN_OUT, SAN_DRIVER, SAN_ROWS_DRIVER)) and open(tag).read().strip() == h:
             return SAN_DRIVER
     except OSError:
         pass
     os.makedirs(os.path.dirname(SAN_OUT), exist_ok=True)
     clangxx = os.path.join(os.path.dirname(os.path.dirname(hipcc())), "lib", "llvm", "bin", "clang++")
+    cxx = clangxx if os.path.exists(clangxx) else "clang++"
     cmds = [[hipcc(), "--offload-arch=gfx950", "-fno-gpu-sanitize", *SAN_FLAGS, "-O1", "-std=c++17", "-shared", "-fPIC",
-             "-o", SAN_OUT, SRC],
-            [clangxx if os.path.exists(clangxx) else "clang++", "-std=c++17", "-O1", "-g", *SAN_FLAGS, "-o", SAN_DRIVER,
-             SAN_DRIVER_SRC, SAN_OUT, "-Wl,-rpath," + os.path.dirname(SAN_OUT)]]
+             "-o", SAN_OUT, SRC]]
+    cmds += [[cxx, "-std=c++17", "-O1", "-g", *SAN_FLAGS, "-o", out, src, SAN_OUT, "-Wl,-rpath," + os.path.dirname(SAN_OUT)]
+             for src, out in ((SAN_DRIVER_SRC, SAN_DRIVER), (SAN_ROWS_DRIVER_SRC, SAN_ROWS_DRIVER))]
     for cmd in cmds:
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -102,3 +107,4 @@ if __name__ == "__main__":
     print(OUT)
     if "--sanitized" in sys.argv:
         print(build_sanitized(force="--force" in sys.argv))
+        print(SAN_ROWS_DRIVER)

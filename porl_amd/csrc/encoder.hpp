@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels.hpp"      // RowSrc
+
 namespace porl {
 
 // ---------------------------------------------------------------------------------------------------
@@ -69,6 +71,8 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restric
 //   patch_bn_kernel    : x1 = fma(conv, alpha, beta) for every position (empty patches get beta), NHWC
 // Pixel semantics are costmap_kernel's (kernels.hpp): values > 8 read as 0, beams rolled by n_ang/2, distance bin
 // 0 cleared, python-style wrap of the cross at bin -1.
+// Both kernels only READ the state, through a RowSrc (kernels.hpp): a dense (batch, n_ang + 2) tensor, or rows of a
+// packed replay store picked by an index array and a column offset.
 // ---------------------------------------------------------------------------------------------------
 struct CostmapGeom { int n_ang, n_dist; float dist_inc, ang_inc, deg_min, deg_max, dist_max; };
 
@@ -120,7 +124,7 @@ constexpr int PE_MAX_E = 128;
 
 // One block per sample (grid-stride): all Hp*Wp masks of the sample at once, the non-empty patches compacted into
 // a list, then thread (e, half) adds the values of channel e over its half of the list in list order (fp64).
-__global__ __launch_bounds__(256) void patch_stats_kernel(const float* __restrict__ state, long state_rs, int batch,
+__global__ __launch_bounds__(256) void patch_stats_kernel(const RowSrc state, int batch,
                                                           CostmapGeom g, const float* __restrict__ w, int E,
                                                           double* __restrict__ partial) {
   extern __shared__ float ps_lds[];
@@ -140,7 +144,7 @@ __global__ __launch_bounds__(256) void patch_stats_kernel(const float* __restric
   const int halves = 256 / E >= 2 ? 2 : 1;
   double s = 0, q = 0;
   for (int b = blockIdx.x; b < batch; b += gridDim.x) {
-    const float* st = state + (long)b * state_rs;
+    const float* st = state.row(b);
     __syncthreads();                                             // list/masks of the previous sample are consumed
     for (int i = t; i < P; i += 256) mask[i] = 0ull;
     __syncthreads();
@@ -184,7 +188,7 @@ __global__ __launch_bounds__(256) void patch_stats_kernel(const float* __restric
 // OUT_BF16: the normalised patch embedding leaves as bf16 (the encoder's bf16-activation mode, encoder_bf16.hpp); `out`
 // then points at a (rows, E) bf16 tensor.  The arithmetic up to the store is the fp32 path's.
 template <bool OUT_BF16>
-__global__ __launch_bounds__(256) void patch_bn_kernel(const float* __restrict__ state, long state_rs, CostmapGeom g,
+__global__ __launch_bounds__(256) void patch_bn_kernel(const RowSrc state, CostmapGeom g,
                                                        const float* __restrict__ w, int E, const float* __restrict__ alpha,
                                                        const float* __restrict__ beta, float* __restrict__ out, int rows_per_block) {
   extern __shared__ float ps_lds[];
@@ -192,6 +196,7 @@ __global__ __launch_bounds__(256) void patch_bn_kernel(const float* __restrict__
   unsigned long long* mask = reinterpret_cast<unsigned long long*>(ps_lds + PE_K * E);
   const int t = threadIdx.x, e4n = E >> 2, Wp = g.n_dist >> 2, Hp = g.n_ang >> 2;
   const long b = blockIdx.y;
+  const float* __restrict__ st = state.row(b);
   for (int i = t; i < PE_K * E; i += 256) {
     const int e = i / PE_K, k = i - e * PE_K;
     wl[k * E + e] = w[i];
@@ -202,7 +207,7 @@ __global__ __launch_bounds__(256) void patch_bn_kernel(const float* __restrict__
   __syncthreads();                        // the previous row's masks are no longer read (first trip: the weight is parked)
   for (int i = t; i < Wp; i += 256) mask[i] = 0ull;
   __syncthreads();
-  patch_row_masks(state + b * state_rs, g, py, mask, t);
+  patch_row_masks(st, g, py, mask, t);
   __syncthreads();
   float* orow = out + (b * Hp + py) * (long)Wp * (OUT_BF16 ? E / 2 : E);      // bf16 rows are half as long
   for (int i = t; i < Wp * e4n; i += 256) {

@@ -485,13 +485,13 @@ int porl_enc_weights_changed(porl_enc* h) {
   return PORL_OK;
 }
 
-int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch, int32_t training, const float* drop_scale,
-                     float* features, int64_t feat_rs, void* stream) {
-  if (!h) PORL_FAIL(PORL_ERR_INVALID, "null engine");
-  if (!h->bound) PORL_FAIL(PORL_ERR_UNBOUND, "porl_enc_bind() has not been called");
-  if (!state || !features || batch < 1 || batch > h->cfg.max_batch)
-    PORL_FAIL(PORL_ERR_INVALID, "need 1 <= batch <= max_batch (%d)", h->cfg.max_batch);
-  if (feat_rs < h->cfg.num_classes || feat_rs > (1 << 20)) PORL_FAIL(PORL_ERR_INVALID, "bad feature row stride");
+}  // extern "C"
+
+namespace {
+// The forward on a row source.  `state` is the caller's own dense tensor (porl_enc_forward: entries > 8 are zeroed in it
+// afterwards, the reference's side effect) or null (porl_enc_forward_rows: the source is only read).
+int enc_forward_src(porl_enc* h, const RowSrc& src, float* state, int64_t state_rs, int32_t batch, int32_t training,
+                    const float* drop_scale, float* features, int64_t feat_rs, void* stream) {
   DevGuard _dg(h->device);
   hipStream_t s = (hipStream_t)stream;
   const porl_enc_cfg& c = h->cfg;
@@ -556,7 +556,7 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_stats));
         lds_attr = lds_stats;
       }
-      hipLaunchKernelGGL(patch_stats_kernel, dim3(nblk), dim3(256), lds_stats, s, state, (long)state_rs, batch, gm,
+      hipLaunchKernelGGL(patch_stats_kernel, dim3(nblk), dim3(256), lds_stats, s, src, batch, gm,
                          h->params + h->w_patch, E, partial);
       PORL_HIP(hipGetLastError());
     }
@@ -573,19 +573,24 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
       rpb = std::min(rpb, h->Hp);
       const dim3 grid(cdiv(h->Hp, rpb), batch);
       if (fused16)
-        hipLaunchKernelGGL(patch_bn_kernel<true>, grid, dim3(256), lds, s, state, (long)state_rs, gm,
+        hipLaunchKernelGGL(patch_bn_kernel<true>, grid, dim3(256), lds, s, src, gm,
                            h->params + h->w_patch, E, W + bn.alpha, W + bn.beta, x1, rpb);
       else
-        hipLaunchKernelGGL(patch_bn_kernel<false>, grid, dim3(256), lds, s, state, (long)state_rs, gm,
+        hipLaunchKernelGGL(patch_bn_kernel<false>, grid, dim3(256), lds, s, src, gm,
                            h->params + h->w_patch, E, W + bn.alpha, W + bn.beta, x1, rpb);
       PORL_HIP(hipGetLastError());
     }
-    const long n = (long)batch * (c.n_ang + 2);       // the reference's in-place side effect (util/costmap.py:17)
-    hipLaunchKernelGGL(clamp_gt8_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 1024)), dim3(256), 0, s, state,
-                       (long)state_rs, c.n_ang + 2, batch);
-    PORL_HIP(hipGetLastError());
+    if (state) {                                        // the reference's in-place side effect (util/costmap.py:17)
+      const long n = (long)batch * (c.n_ang + 2);
+      hipLaunchKernelGGL(clamp_gt8_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 1024)), dim3(256), 0, s, state,
+                         (long)state_rs, c.n_ang + 2, batch);
+      PORL_HIP(hipGetLastError());
+    }
   } else {
-    PORL_TRY(porl_state2costmap(state, state_rs, batch, c.n_ang, c.n_dist, W + h->ws_img, stream));
+    // rasterise (+ the in-place clamp on a caller's own tensor), then the dense 4x4 convolution; store rows go through
+    // the rasteriser alone, which only reads
+    if (state) PORL_TRY(porl_state2costmap(state, state_rs, batch, c.n_ang, c.n_dist, W + h->ws_img, stream));
+    else PORL_TRY(costmap_rasterise(src, batch, c.n_ang, c.n_dist, W + h->ws_img, s));
     {
       ProfScope ps("patch_embed_kernel", s, 2.0 * rows1 * E * 48, 4.0 * (3.0 * batch * c.n_ang * c.n_dist + rows1 * E));
       const size_t lds = (size_t)(12 * c.n_dist + PE_K * E) * sizeof(float);
@@ -688,6 +693,39 @@ int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch,
   PORL_TRY(enc_gemm_rows(h, s, W + h->ws_feat, c.feature_dim, batch, h->params + h->w_head, c.num_classes, c.feature_dim,
                          features, (int)feat_rs, h->params + h->b_head, ACT_NONE));
   return PORL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int porl_enc_forward(porl_enc* h, float* state, int64_t state_rs, int32_t batch, int32_t training, const float* drop_scale,
+                     float* features, int64_t feat_rs, void* stream) {
+  if (!h) PORL_FAIL(PORL_ERR_INVALID, "null engine");
+  if (!h->bound) PORL_FAIL(PORL_ERR_UNBOUND, "porl_enc_bind() has not been called");
+  if (!state || !features || batch < 1 || batch > h->cfg.max_batch)
+    PORL_FAIL(PORL_ERR_INVALID, "need 1 <= batch <= max_batch (%d)", h->cfg.max_batch);
+  if (feat_rs < h->cfg.num_classes || feat_rs > (1 << 20)) PORL_FAIL(PORL_ERR_INVALID, "bad feature row stride");
+  return enc_forward_src(h, RowSrc{state, (long)state_rs, nullptr, 0}, state, state_rs, batch, training, drop_scale, features,
+                         feat_rs, stream);
+}
+
+int porl_enc_forward_rows(porl_enc* h, const float* rows, int64_t row_stride, int64_t n_rows, const int64_t* idx,
+                          int32_t col_offset, int32_t batch, int32_t training, const float* drop_scale, float* features,
+                          int64_t feat_rs, void* stream) {
+  if (!h) PORL_FAIL(PORL_ERR_INVALID, "null engine");
+  if (!h->bound) PORL_FAIL(PORL_ERR_UNBOUND, "porl_enc_bind() has not been called");
+  if (!rows) PORL_FAIL(PORL_ERR_INVALID, "null rows");
+  if (!idx) PORL_FAIL(PORL_ERR_INVALID, "null idx");
+  if (!features) PORL_FAIL(PORL_ERR_INVALID, "null features");
+  if (batch < 1 || batch > h->cfg.max_batch) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", batch, h->cfg.max_batch);
+  if (n_rows < 1) PORL_FAIL(PORL_ERR_INVALID, "n_rows %lld must be at least 1", (long long)n_rows);
+  if (col_offset < 0 || (int64_t)col_offset + h->cfg.n_ang + 2 > row_stride)
+    PORL_FAIL(PORL_ERR_INVALID, "col_offset %d: a state of %d floats does not fit a row of stride %lld there", col_offset,
+              h->cfg.n_ang + 2, (long long)row_stride);
+  if (feat_rs < h->cfg.num_classes || feat_rs > (1 << 20))
+    PORL_FAIL(PORL_ERR_INVALID, "feat_rs %lld outside [num_classes = %d, 2^20]", (long long)feat_rs, h->cfg.num_classes);
+  return enc_forward_src(h, RowSrc{rows, (long)row_stride, idx, col_offset}, nullptr, 0, batch, training, drop_scale, features,
+                         feat_rs, stream);
 }
 
 }  // extern "C"

@@ -686,6 +686,69 @@ __global__ __launch_bounds__(256) void sampled_batch_kernel(const SampledBatchAr
   }
 }
 
+// A read-only source of sample rows: sample b is the floats at base + (idx ? idx[b] : b) * stride + col.  Dense callers
+// pass idx = nullptr, col = 0; a packed replay store is read in place through its index array and a column offset
+// (s at 0, s' at S + 1).  Nothing is assumed about the alignment of a row beyond 4 bytes.
+struct RowSrc {
+  const float* base; long stride; const int64_t* idx; int col;
+  __device__ __forceinline__ const float* row(long b) const { return base + (idx ? (long)idx[b] : b) * stride + col; }
+};
+
+// gather + split for GIVEN indices: batch row i <- packed replay row idx[i], like sampled_batch_kernel, except that the
+// observations may come from feature matrices (an encoder ran on the rows) instead of the rows' own state columns, and
+// that the policy target can be staged as the encoder's > 8 clamp would have left it.  One wave per batch row.
+//   S = state columns of a row, F = columns of xs / xn (cfg.obs_dim; == S when obs_feat is null)
+struct IndexedBatchArgs {
+  const float* rows; long row_stride; const int64_t* idx;
+  int batch, S, F, D, Sp, Dp, target_is_action, clamp_target;
+  const float* obs_feat; long obs_rs; const float* next_feat; long next_rs;
+  float* xs; float* xn; float* xt; float* rew; float* term;
+};
+
+__global__ __launch_bounds__(256) void indexed_batch_kernel(const IndexedBatchArgs a) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= a.batch) return;
+  const float* __restrict__ src = a.rows + a.idx[i] * a.row_stride;
+  const int S = a.S, F = a.F;
+  float* xs = a.xs + (size_t)i * a.Sp;
+  float* xn = a.xn + (size_t)i * a.Sp;
+  if (a.obs_feat) {
+    const float* __restrict__ fo = a.obs_feat + (long)i * a.obs_rs;
+    const float* __restrict__ fn = a.next_feat + (long)i * a.next_rs;
+    // 16-byte lanes when every row of both matrices and of the staging buffers starts on a 16-byte boundary
+    const bool vec = (F & 3) == 0 && (a.Sp & 3) == 0 && (a.obs_rs & 3) == 0 && (a.next_rs & 3) == 0 &&
+                     ((reinterpret_cast<uintptr_t>(a.obs_feat) | reinterpret_cast<uintptr_t>(a.next_feat) |
+                       reinterpret_cast<uintptr_t>(a.xs) | reinterpret_cast<uintptr_t>(a.xn)) & 15) == 0;
+    if (vec) {
+      for (int c = lane * 4; c < a.Sp; c += 256) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(xs + c) = c < F ? *reinterpret_cast<const float4*>(fo + c) : z;
+        *reinterpret_cast<float4*>(xn + c) = c < F ? *reinterpret_cast<const float4*>(fn + c) : z;
+      }
+    } else {
+      for (int c = lane; c < a.Sp; c += 64) {
+        xs[c] = c < F ? fo[c] : 0.f;
+        xn[c] = c < F ? fn[c] : 0.f;
+      }
+    }
+  } else {
+    for (int c = lane; c < a.Sp; c += 64) {
+      xs[c] = c < F ? src[c] : 0.f;
+      xn[c] = c < F ? src[S + 1 + c] : 0.f;
+    }
+  }
+  const int toff = a.target_is_action ? 2 * S + 2 : S + 1;
+  for (int c = lane; c < a.Dp; c += 64) {
+    float v = c < a.D ? src[toff + c] : 0.f;
+    if (a.clamp_target && v > 8.f) v = 0.f;
+    a.xt[(size_t)i * a.Dp + c] = v;
+  }
+  if (lane == 0) {
+    a.rew[i] = src[S];
+    a.term[i] = src[2 * S + 1];
+  }
+}
+
 // out[i] = base + perm_{seed,step}(first + i): `batch` consecutive positions of one keyed permutation of [0, n)
 __global__ void sample_indices_kernel(int64_t n, int batch, uint64_t seed, uint64_t step, int hb,
                                       int64_t base, int64_t first, int64_t* __restrict__ out) {
@@ -1098,17 +1161,18 @@ __global__ __launch_bounds__(256) void cql_penalty_kernel(const float* __restric
 // state2costmap (util/costmap.py:7-64): (B, n_ang + 2) lidar ranges + relative goal -> (B, 3, n_ang, n_dist)
 // polar occupancy image.  One block per (angle row, sample), one thread per distance bin; the image is
 // written directly in channel-major order (the reference builds (B, n_ang, n_dist, 3) and permutes).
-//   * values > 8 count as 0 everywhere and are zeroed IN PLACE like the reference does (:17)
+//   * values > 8 count as 0 everywhere; the reference also zeroes them IN PLACE (:17), which clamp_gt8_kernel does
+//     afterwards for callers that own the tensor — this kernel only reads, so it can rasterise rows of a replay store
 //   * channel 0: one-hot of int(range / d_inc) per beam, beams rolled by n_ang/2, bin 0 cleared
 //   * all channels: 3-pixel cross at the goal's (angle bin, distance bin); index -1 wraps to the last bin
 //     exactly as the reference's advanced indexing does (dist bin 0 lights bin n_dist-1)
 // Ranges that would index past n_dist-1 make the reference raise; here they are dropped.
 // ---------------------------------------------------------------------------------------------------
-__global__ void costmap_kernel(float* __restrict__ state, long state_stride, int n_ang, int n_dist,
+__global__ void costmap_kernel(const RowSrc state, int n_ang, int n_dist,
                                float dist_inc, float ang_inc, float deg_min, float deg_max, float dist_max,
                                float* __restrict__ out) {
   const int r = blockIdx.x, b = blockIdx.y;
-  float* st = state + (long)b * state_stride;
+  const float* __restrict__ st = state.row(b);
   auto rd = [&](int i) { const float v = st[i]; return v > 8.f ? 0.f : v; };
   const int src = (r - n_ang / 2 + n_ang) % n_ang;              // torch.roll(idx, n_ang/2, 1)
   const long beam_bin = (long)(rd(src) / dist_inc);             // .to(torch.long): truncation

@@ -739,6 +739,53 @@ int porl_iql_load_batch_sampled(porl_iql* h, int32_t batch, const float* rows, i
   return PORL_OK;
 }
 
+int porl_iql_load_batch_indexed(porl_iql* h, int32_t batch, const float* rows, int64_t row_stride, int64_t n_rows,
+                                const int64_t* idx, int32_t state_dim, int32_t act_dim, int32_t target_is_action,
+                                int32_t clamp_target_gt8, const float* obs_feat, int64_t obs_rs, const float* next_feat,
+                                int64_t next_rs, void* stream) {
+  PORL_TRY(check_ready(h, false));
+  // every argument is judged before the first HIP call
+  if (batch < 1 || batch > h->cfg.max_batch) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", batch, h->cfg.max_batch);
+  if (!rows) PORL_FAIL(PORL_ERR_INVALID, "null rows");
+  if (!idx) PORL_FAIL(PORL_ERR_INVALID, "null idx");
+  if (n_rows < 1) PORL_FAIL(PORL_ERR_INVALID, "n_rows %lld must be at least 1", (long long)n_rows);
+  const int F = h->cfg.obs_dim, D = h->cfg.pol_out_dim;
+  if (state_dim < 1 || act_dim < 0) PORL_FAIL(PORL_ERR_INVALID, "state_dim %d / act_dim %d out of range", state_dim, act_dim);
+  if (row_stride < 2 * (int64_t)state_dim + 2 + act_dim)
+    PORL_FAIL(PORL_ERR_INVALID, "row_stride %lld shorter than 2*state_dim+2+act_dim = %lld", (long long)row_stride,
+              2 * (long long)state_dim + 2 + act_dim);
+  if ((obs_feat == nullptr) != (next_feat == nullptr))
+    PORL_FAIL(PORL_ERR_INVALID, "obs_feat and next_feat must be given together (%s is null)", obs_feat ? "next_feat" : "obs_feat");
+  if (obs_feat && obs_rs < F) PORL_FAIL(PORL_ERR_INVALID, "obs_rs %lld below obs_dim %d", (long long)obs_rs, F);
+  if (next_feat && next_rs < F) PORL_FAIL(PORL_ERR_INVALID, "next_rs %lld below obs_dim %d", (long long)next_rs, F);
+  if (!obs_feat && state_dim != F)
+    PORL_FAIL(PORL_ERR_INVALID, "state_dim %d != obs_dim %d and no feature matrices given", state_dim, F);
+  if (target_is_action ? D != act_dim : D != state_dim)
+    PORL_FAIL(PORL_ERR_INVALID, "policy target width mismatch: pol_out_dim %d vs %s %d", D, target_is_action ? "act_dim" : "state_dim",
+              target_is_action ? act_dim : state_dim);
+  DevGuard _dg(h->device);
+  float* W = h->buf.workspace;
+  if (h->mode & PORL_IQL_MODE_TWO_SLOTS) h->slot = (h->slot + 1) % PORL_IQL_SLOTS;
+  IndexedBatchArgs a{};
+  a.rows = rows; a.row_stride = (long)row_stride; a.idx = idx;
+  a.batch = batch; a.S = state_dim; a.F = F; a.D = D; a.Sp = h->Sp; a.Dp = h->Dp;
+  a.target_is_action = target_is_action; a.clamp_target = clamp_target_gt8;
+  a.obs_feat = obs_feat; a.obs_rs = (long)obs_rs; a.next_feat = next_feat; a.next_rs = (long)next_rs;
+  a.xs = W + h->ws.xs_slot[h->slot]; a.xn = W + h->ws.xn; a.xt = W + h->ws.xt_slot[h->slot]; a.rew = W + h->ws.rew; a.term = W + h->ws.term;
+  {
+    g_phase = "V1.";
+    ProfScope ps("indexed_batch_kernel", (hipStream_t)stream, 0.0, 4.0 * batch * (2.0 * h->Sp + h->Dp + 2) * 2.0);
+    hipLaunchKernelGGL(indexed_batch_kernel, dim3(cdiv(batch, 4)), dim3(256), 0, (hipStream_t)stream, a);
+    g_phase = "";
+  }
+  PORL_HIP(hipGetLastError());
+  h->batch = batch;
+  h->have_pol_target = true;
+  h->pol_prefetched = false;
+  h->pol_fwd_done = false;
+  return PORL_OK;
+}
+
 int porl_iql_set_mode(porl_iql* h, int32_t mode) {
   if (!h) PORL_FAIL(PORL_ERR_INVALID, "null engine");
   if (mode & ~(PORL_IQL_MODE_TWO_SLOTS | PORL_IQL_MODE_FOLD_COMBINE | PORL_IQL_MODE_SHORT_BLOCKS)) PORL_FAIL(PORL_ERR_INVALID, "unknown mode bits");
@@ -1841,21 +1888,28 @@ int porl_tune_set_ptr(const char* key, void* ptr) {
   PORL_FAIL(PORL_ERR_INVALID, "unknown tuning key '%s'", key);
 }
 
-int porl_state2costmap(float* state, int64_t state_rs, int32_t batch, int32_t n_ang, int32_t n_dist, float* out,
-                        void* stream) {
-  if (!state || !out || batch < 1 || n_ang < 4 || n_dist < 4) PORL_FAIL(PORL_ERR_INVALID, "bad costmap arguments");
-  if (batch > 65535) PORL_FAIL(PORL_ERR_INVALID, "batch > 65535");
-  DevGuard _dg(device_of(out));
-  hipStream_t s = (hipStream_t)stream;
+// the rasteriser alone on any row source (reads only): porl_state2costmap, and the encoder's dense patch path on rows of a
+// replay store (encoder_api.inc)
+static int costmap_rasterise(const RowSrc& src, int32_t batch, int32_t n_ang, int32_t n_dist, float* out, hipStream_t s) {
   // constants exactly as util/costmap.py:19-20,34,45 forms them (python doubles rounded to fp32 at the tensor op)
   const double pi = 3.14159265358979323846;
   const float dist_inc = (float)((4.0 + 1e-4) / n_dist);
   const float ang_inc = (float)((2.0 * pi + 1e-4) / n_ang);
   const float deg_min = (float)(-pi + (2.0 * pi + 2e-4) / n_ang), deg_max = (float)(pi - (2.0 * pi + 2e-4) / n_ang);
   const float dist_max = (float)(4.0 - 4.0 / n_dist);
-  hipLaunchKernelGGL(costmap_kernel, dim3(n_ang, batch), dim3(std::min(256, n_dist)), 0, s, state, (long)state_rs, n_ang,
-                     n_dist, dist_inc, ang_inc, deg_min, deg_max, dist_max, out);
+  hipLaunchKernelGGL(costmap_kernel, dim3(n_ang, batch), dim3(std::min(256, n_dist)), 0, s, src, n_ang, n_dist, dist_inc,
+                     ang_inc, deg_min, deg_max, dist_max, out);
   PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+int porl_state2costmap(float* state, int64_t state_rs, int32_t batch, int32_t n_ang, int32_t n_dist, float* out,
+                        void* stream) {
+  if (!state || !out || batch < 1 || n_ang < 4 || n_dist < 4) PORL_FAIL(PORL_ERR_INVALID, "bad costmap arguments");
+  if (batch > 65535) PORL_FAIL(PORL_ERR_INVALID, "batch > 65535");
+  DevGuard _dg(device_of(out));
+  hipStream_t s = (hipStream_t)stream;
+  PORL_TRY(costmap_rasterise(RowSrc{state, (long)state_rs, nullptr, 0}, batch, n_ang, n_dist, out, s));
   const long n = (long)batch * (n_ang + 2);
   hipLaunchKernelGGL(clamp_gt8_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 1024)), dim3(256), 0, s, state,
                      (long)state_rs, n_ang + 2, batch);

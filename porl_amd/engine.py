@@ -246,6 +246,40 @@ class IqlEngine:
         self.last_batch = batch
         return batch
 
+    def load_batch_indexed(self, rows, idx, state_dim, act_dim, target_is_action, obs_feat=None, next_feat=None,
+                           clamp_target_gt8=False):
+        """Stage rows `idx` (int64, on the device) of a packed-row store [s | r | s' | d | a] (one kernel, the store is
+        only read): rewards, terminals and the policy target from the rows, observations from the rows too, or from
+        the (B, obs_dim) feature matrices `obs_feat` / `next_feat` an encoder made of them.  Index range is the caller's
+        contract, as for `gather_rows`."""
+        self._ensure_bound()
+        if rows.device != self.device or rows.dtype != torch.float32 or rows.dim() != 2 or rows.stride(1) != 1:
+            raise RuntimeError("replay rows must be a 2-D fp32 tensor on the engine's device")
+        if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device:
+            raise RuntimeError(f"indices: expected a contiguous 1-D int64 tensor on {self.device}, got {idx.dtype} "
+                               f"{tuple(idx.shape)} on {idx.device}")
+        B = idx.numel()
+        if B > self.cfg.max_batch:
+            raise RuntimeError(f"batch {B} exceeds engine max_batch {self.cfg.max_batch}")
+        if (obs_feat is None) != (next_feat is None):
+            raise RuntimeError("obs_feat and next_feat must be given together")
+        if obs_feat is not None:
+            for t in (obs_feat, next_feat):
+                if t.device != self.device:
+                    raise RuntimeError(f"feature tensor on {t.device}, engine on {self.device}")
+            obs_feat, next_feat = self._mat(obs_feat, self.cfg.obs_dim, "features"), self._mat(next_feat, self.cfg.obs_dim, "next features")
+            if obs_feat.shape[0] != B or next_feat.shape[0] != B:
+                raise RuntimeError(f"features: expected {B} rows, got {obs_feat.shape[0]} and {next_feat.shape[0]}")
+        # keep references alive until the load kernel has run (stream-ordered; torch caches the memory)
+        self._held = (idx, obs_feat, next_feat)
+        N.check(self._lib.porl_iql_load_batch_indexed(
+            self._h, B, N.ptr(rows), rows.stride(0), rows.shape[0], N.ptr(idx), int(state_dim), int(act_dim),
+            int(bool(target_is_action)), int(bool(clamp_target_gt8)), N.ptr(obs_feat),
+            0 if obs_feat is None else obs_feat.stride(0), N.ptr(next_feat), 0 if next_feat is None else next_feat.stride(0),
+            N.current_stream_ptr(self.device)), "porl_iql_load_batch_indexed")
+        self.last_batch = B
+        return B
+
     def set_stats(self, stats):
         """Point the loss statistics of the following updates at `stats` (>= 8 fp32 on the device)."""
         self._ensure_bound()
