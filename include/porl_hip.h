@@ -667,6 +667,54 @@ int porl_astar_label(const float* rows, int64_t row_stride, int64_t n_rows, cons
                      int32_t* path_len, int32_t* status, int32_t* sweeps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Trajectory-level dataset passes (util/util.py:67-138; kernels in csrc/episodes.hpp).  A done flag is SET iff
+ * d != 0.0f (NaN set, -0.0 clear: np.where(dones) / `if d`).  Flag and reward vectors are read in place through
+ * (base, stride in floats, n_rows): a dense vector or one column of a packed row store.
+ * --------------------------------------------------------------------------------------------- */
+
+/* int64 words of workspace porl_episode_count / _fill need for n_rows rows (-1 when n_rows is outside [1, 2^40]);
+ * also reports the scan's tile constants: rows per block and partials per sweep of the partial scan (either pointer
+ * may be null). */
+int64_t porl_episode_workspace(int64_t n_rows, int32_t* rows_per_block, int32_t* partials_per_sweep);
+
+/* The episode table, first call (extract_done_makers, util/util.py:83-87; with cap > 0 the walk of return_range,
+ * :67-80, where an episode also closes when ep_len == cap): counts the rows that close an episode.  On return (in stream
+ * order) workspace[0] = K, the number of closed episodes, and workspace[1] = the rows after the last of them (the
+ * trailing run the reference drops, :77-78).  The rest of the workspace carries the block offsets to porl_episode_fill.
+ * cap 0 = none.  Separate launches (block partials, a scan of the partials, the pass proper): no block waits on
+ * another.  The caller reads K back — the one synchronisation per dataset. */
+int porl_episode_count(const float* flags, int64_t stride, int64_t n_rows, int64_t cap, int64_t* workspace, void* stream);
+
+/* Second call, same flags / stride / n_rows / cap and the workspace the count left: starts[k], ends[k] (int64, k <
+ * n_episodes = K) of every closed episode, ascending; starts[0] = 0, starts[k] = ends[k-1] + 1.  No store goes past
+ * n_episodes entries. */
+int porl_episode_fill(const float* flags, int64_t stride, int64_t n_rows, int64_t cap, const int64_t* workspace,
+                      int64_t n_episodes, int64_t* starts, int64_t* ends, void* stream);
+
+/* return_range (util/util.py:67-80): returns[k] = the fp64 sum of the fp32 rewards of rows starts[k] .. ends[k] added in
+ * row order from 0.0 — bit for bit the reference's Python float.  With range_out (3 doubles) also min(returns),
+ * max(returns) over the returns that are not NaN and range_out[2] = 1.0 if any return is NaN, else 0.0; range_ws is
+ * then 4 * 256 int64 words of scratch. */
+int porl_episode_returns(const float* rewards, int64_t stride, int64_t n_rows, const int64_t* starts, const int64_t* ends,
+                         int64_t n_episodes, double* returns, int64_t* range_ws, double* range_out, void* stream);
+
+/* _sample_indces (util/util.py:90-116): per sample i < batch a trajectory `traj` in [0, n_episodes) and u1, u2 in [0, 1);
+ * t1 = floor(u1 * (lengths[traj] - 1)), t2 = floor(u2 * lengths[traj]) in fp64; start[i] = starts[traj] + min(t1, t2),
+ * goal[i] = starts[traj] + max(t1, t2).  The draws are the caller's (traj, u1, u2 all non-null) or a counter-based
+ * stream keyed by (seed, step, i, stream 0|1|2): x = sm64(sm64(seed ^ sm64(step)) ^ sm64(3 i + stream)) with splitmix64's
+ * output function sm64, traj = mulhi64(x0, n_episodes), u = (x >> 11) * 2^-53.  traj_out / u1_out / u2_out (optional)
+ * receive the draws used.  A given traj outside the table yields start = goal = -1. */
+int porl_hindsight_pairs(const int64_t* starts, const int64_t* lengths, int64_t n_episodes, int32_t batch, uint64_t seed,
+                         uint64_t step, const int64_t* traj, const double* u1, const double* u2, int64_t* start, int64_t* goal,
+                         int64_t* traj_out, double* u1_out, double* u2_out, void* stream);
+
+/* rvs_sample_batch (util/util.py:129-138) in the packed wire format [s | r | s' | d | a]:
+ * out[i] = [ rows[start[i]][:obs_dim] | 0 | rows[goal[i]][:obs_dim] | 0 | rows[start[i]][2*obs_dim + 2 ..] ].
+ * One wave per batch row; a start or goal outside [0, n_rows) makes the output row NaN instead of a stray read. */
+int porl_gather_pairs(const float* rows, int64_t row_stride, int64_t n_rows, const int64_t* start, const int64_t* goal,
+                      int32_t batch, int32_t obs_dim, int32_t act_dim, float* out, int64_t out_stride, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Costmap encoder engine: FasterNet.forward_cls (agent/fasternet.py:428-438) as built by
  * sorl_train.py:29 `FasterNet(3, args.feature_dim)` — state2costmap, PatchEmbed 4x4s4 + BN (:234-246),
  * depth0 MLPBlocks (:141-194, Partial_conv3 :110-138), PatchMerging 2x2s2 + BN (:249-261), depth1

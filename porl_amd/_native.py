@@ -37,6 +37,8 @@ SYMBOLS = [
     "porl_enc_workspace_floats", "porl_enc_tensors", "porl_enc_norms", "porl_enc_blocks",
     "porl_enc_tensor_info", "porl_enc_norm_info", "porl_enc_bind", "porl_enc_weights_changed", "porl_enc_forward", "porl_enc_forward_rows",
     "porl_enc_tap_info",
+    "porl_episode_workspace", "porl_episode_count", "porl_episode_fill", "porl_episode_returns", "porl_hindsight_pairs",
+    "porl_gather_pairs",
 ]
 
 
@@ -273,6 +275,13 @@ def _declare(lib):
     lib.porl_enc_weights_changed.argtypes = [vp]
     lib.porl_enc_forward.argtypes = [vp, vp, i64, i32, i32, vp, vp, i64, vp]
     lib.porl_enc_forward_rows.argtypes = [vp, vp, i64, i64, vp, i32, i32, i32, vp, vp, i64, vp]
+    lib.porl_episode_workspace.argtypes = [i64, C.POINTER(i32), C.POINTER(i32)]
+    lib.porl_episode_workspace.restype = i64
+    lib.porl_episode_count.argtypes = [vp, i64, i64, i64, vp, vp]
+    lib.porl_episode_fill.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, vp]
+    lib.porl_episode_returns.argtypes = [vp, i64, i64, vp, vp, i64, vp, vp, vp, vp]
+    lib.porl_hindsight_pairs.argtypes = [vp, vp, i64, i32, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.porl_gather_pairs.argtypes = [vp, i64, i64, vp, vp, i32, i32, i32, vp, i64, vp]
     lib.porl_prof_enable.argtypes = [C.c_int]
     lib.porl_prof_read.argtypes = [C.POINTER(ProfEntry), C.c_int]
     for name in SYMBOLS:

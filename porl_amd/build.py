@@ -69,20 +69,24 @@ SAN_DRIVER = os.path.join(HERE, "lib", "abi_reject_san")
 # second driver, same library: the entry points that read a packed replay store in place (tests/test_enc_replay_host.py)
 SAN_ROWS_DRIVER_SRC = os.path.join(os.path.dirname(HERE), "tests", "helpers", "abi_reject_rows.cpp")
 SAN_ROWS_DRIVER = os.path.join(HERE, "lib", "abi_reject_rows_san")
+# third driver: the episode-table / hindsight-pair entry points (tests/test_episodes_host.py)
+SAN_EPISODES_DRIVER_SRC = os.path.join(os.path.dirname(HERE), "tests", "helpers", "abi_reject_episodes.cpp")
+SAN_EPISODES_DRIVER = os.path.join(HERE, "lib", "abi_reject_episodes_san")
 SAN_FLAGS = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 
 def build_sanitized(force=False, verbose=True):
     """The same translation unit with AddressSanitizer + UBSan on the HOST half (planner, validation, layout code; the
     device half is compiled as usual and never runs), plus the drivers that walk the rejected-argument paths
-    (tests/helpers/abi_reject.cpp -> SAN_DRIVER, tests/helpers/abi_reject_rows.cpp -> SAN_ROWS_DRIVER).  CPU-only check:
-    GPU sanitizers are not available on this pool.  Returns SAN_DRIVER; cached by source hash like the product
-    library."""
+    (tests/helpers/abi_reject.cpp -> SAN_DRIVER, tests/helpers/abi_reject_rows.cpp -> SAN_ROWS_DRIVER,
+    tests/helpers/abi_reject_episodes.cpp -> SAN_EPISODES_DRIVER).  CPU-only check: GPU sanitizers are not available on
+    this pool.  Returns SAN_DRIVER; cached by source hash like the product library."""
     import hashlib
-    h = hashlib.sha256((source_hash() + open(SAN_DRIVER_SRC).read() + open(SAN_ROWS_DRIVER_SRC).read()).encode()).hexdigest()
+    drivers = ((SAN_DRIVER_SRC, SAN_DRIVER), (SAN_ROWS_DRIVER_SRC, SAN_ROWS_DRIVER), (SAN_EPISODES_DRIVER_SRC, SAN_EPISODES_DRIVER))
+    h = hashlib.sha256((source_hash() + "".join(open(src).read() for src, _ in drivers)).encode()).hexdigest()
     tag = SAN_OUT + ".srchash"
     try:
-        if not force and all(os.path.exists(f) for f in (SAN_OUT, SAN_DRIVER, SAN_ROWS_DRIVER)) and open(tag).read().strip() == h:
+        if not force and all(os.path.exists(f) for f in (SAN_OUT, *(out for _, out in drivers))) and open(tag).read().strip() == h:
             return SAN_DRIVER
     except OSError:
         pass
@@ -92,7 +96,7 @@ def build_sanitized(force=False, verbose=True):
     cmds = [[hipcc(), "--offload-arch=gfx950", "-fno-gpu-sanitize", *SAN_FLAGS, "-O1", "-std=c++17", "-shared", "-fPIC",
              "-o", SAN_OUT, SRC]]
     cmds += [[cxx, "-std=c++17", "-O1", "-g", *SAN_FLAGS, "-o", out, src, SAN_OUT, "-Wl,-rpath," + os.path.dirname(SAN_OUT)]
-             for src, out in ((SAN_DRIVER_SRC, SAN_DRIVER), (SAN_ROWS_DRIVER_SRC, SAN_ROWS_DRIVER))]
+             for src, out in drivers]
     for cmd in cmds:
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -108,3 +112,4 @@ if __name__ == "__main__":
     if "--sanitized" in sys.argv:
         print(build_sanitized(force="--force" in sys.argv))
         print(SAN_ROWS_DRIVER)
+        print(SAN_EPISODES_DRIVER)

@@ -24,6 +24,7 @@
 #include "per_online.hpp"
 #include "bcq_mask.hpp"
 #include "astar.hpp"
+#include "episodes.hpp"
 
 using namespace porl;
 
@@ -2011,3 +2012,4 @@ int porl_prof_read(porl_prof_entry* out, int max_entries) {
 #include "qnet_api.inc"
 #include "encoder_api.inc"
 #include "iqn_api.inc"
+#include "episodes_api.inc"

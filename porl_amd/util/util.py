@@ -68,3 +68,24 @@ def update_exponential_moving_average(target, source, alpha):
                 E.ema(t, s, alpha)
             else:
                 t.mul_(1.0 - alpha).add_(s, alpha=alpha)
+
+
+def extract_done_makers(dones):
+    """Episode table (starts, ends, lengths) of a done-flag vector (reference util/util.py:83-87), on the device:
+    porl_amd.dataloader.episodes.extract_done_makers."""
+    from ..dataloader import episodes
+    return episodes.extract_done_makers(dones)
+
+
+def return_range(dataset, max_episode_steps):
+    """(min, max) episode return (reference util/util.py:67-80), on the device:
+    porl_amd.dataloader.episodes.return_range."""
+    from ..dataloader import episodes
+    return episodes.return_range(dataset, max_episode_steps)
+
+
+def rvs_sample_batch(dataset, batch_size):
+    """Hindsight-goal minibatch (reference util/util.py:129-138) from a PackedReplay, on the device:
+    porl_amd.dataloader.episodes.rvs_sample_batch."""
+    from ..dataloader import episodes
+    return episodes.rvs_sample_batch(dataset, batch_size)
