@@ -715,6 +715,39 @@ int porl_gather_pairs(const float* rows, int64_t row_stride, int64_t n_rows, con
                       int32_t batch, int32_t obs_dim, int32_t act_dim, float* out, int64_t out_stride, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Stable two-way partition of the rows of a resident store (generate_test_generlaization_data, util/util.py:219-238;
+ * kernels in csrc/partition.hpp).  Rows are read in place through (rows, stride_bytes, n_rows) — a dense store, a
+ * row-strided view or a column block of a wider one — and copied as raw 32-bit words (16-byte lanes when both buffers,
+ * the stride and row_bytes allow), so NaN payloads and -0.0 survive.  The input is never written.  A row is HELD iff
+ * held[i] != 0 (form a) or iff both fp32 words box->cx, box->cy of it lie in the box, bounds inclusive, compared in
+ * fp32 (form b; a NaN coordinate is not held — numpy's comparisons in the reference).
+ * --------------------------------------------------------------------------------------------- */
+typedef struct porl_partition_box {
+  int32_t cx, cy;             /* the two fp32 words of a row that are tested */
+  float x_lo, x_hi, y_lo, y_hi;
+} porl_partition_box;
+
+/* int64 words of workspace porl_partition_rows needs for n_rows rows (-1 when n_rows is outside [1, 2^36]); also
+ * reports the tile constants: rows per block and partials per sweep of the one-wave scan (either pointer may be null). */
+int64_t porl_partition_workspace(int64_t n_rows, int32_t* rows_per_block, int32_t* partials_per_sweep);
+
+/* mask[i] = 1 if row i is held by `box`, else 0 (uint8, n_rows entries): form (b) made storable, for callers that
+ * compact several arrays by one predicate.  One launch. */
+int porl_partition_mask(const void* rows, int64_t stride_bytes, int64_t n_rows, int64_t row_bytes,
+                        const porl_partition_box* box, uint8_t* mask, void* stream);
+
+/* out (n_rows dense rows of row_bytes) = every row that is not held, in input order, then every held row, in input
+ * order: row i goes to rank_kept(i), or to K + (i - rank_kept(i)) when held.  Exactly one of `held` (uint8, n_rows) and
+ * `box` is non-null; with `box` both passes recompute the predicate from the rows and no mask is stored.  `index`
+ * (optional, int64 n_rows) receives the original row numbers in the same arrangement.  On return (in stream order)
+ * workspace[0] = K, the number of kept rows, and workspace[1] = n_rows - K.  Three launches (tile counts, a one-wave scan
+ * of them, recompute-and-scatter): no block waits on another; every store is bounded by n_rows.  row_bytes and
+ * stride_bytes are multiples of 4, row_bytes <= stride_bytes <= 2^22.  The caller reads K back once, to cut the two
+ * views — the only synchronisation. */
+int porl_partition_rows(const void* rows, int64_t stride_bytes, int64_t n_rows, int64_t row_bytes, const uint8_t* held,
+                        const porl_partition_box* box, void* out, int64_t* index, int64_t* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Costmap encoder engine: FasterNet.forward_cls (agent/fasternet.py:428-438) as built by
  * sorl_train.py:29 `FasterNet(3, args.feature_dim)` — state2costmap, PatchEmbed 4x4s4 + BN (:234-246),
  * depth0 MLPBlocks (:141-194, Partial_conv3 :110-138), PatchMerging 2x2s2 + BN (:249-261), depth1

@@ -39,6 +39,7 @@ SYMBOLS = [
     "porl_enc_tap_info",
     "porl_episode_workspace", "porl_episode_count", "porl_episode_fill", "porl_episode_returns", "porl_hindsight_pairs",
     "porl_gather_pairs",
+    "porl_partition_workspace", "porl_partition_mask", "porl_partition_rows",
 ]
 
 
@@ -133,6 +134,10 @@ class AstarParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("resolution", "robot_radius", "min_x", "max_x", "min_y", "max_y", "range_lo",
                                           "range_hi")] + \
                [(n, C.c_int32) for n in ("n_beams", "pose_off", "heading_off", "goal_off")]
+
+
+class PartitionBox(C.Structure):
+    _fields_ = [("cx", C.c_int32), ("cy", C.c_int32)] + [(n, C.c_float) for n in ("x_lo", "x_hi", "y_lo", "y_hi")]
 
 
 class ProfEntry(C.Structure):
@@ -282,6 +287,10 @@ def _declare(lib):
     lib.porl_episode_returns.argtypes = [vp, i64, i64, vp, vp, i64, vp, vp, vp, vp]
     lib.porl_hindsight_pairs.argtypes = [vp, vp, i64, i32, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.porl_gather_pairs.argtypes = [vp, i64, i64, vp, vp, i32, i32, i32, vp, i64, vp]
+    lib.porl_partition_workspace.argtypes = [i64, C.POINTER(i32), C.POINTER(i32)]
+    lib.porl_partition_workspace.restype = i64
+    lib.porl_partition_mask.argtypes = [vp, i64, i64, i64, C.POINTER(PartitionBox), vp, vp]
+    lib.porl_partition_rows.argtypes = [vp, i64, i64, i64, vp, C.POINTER(PartitionBox), vp, vp, vp, vp]
     lib.porl_prof_enable.argtypes = [C.c_int]
     lib.porl_prof_read.argtypes = [C.POINTER(ProfEntry), C.c_int]
     for name in SYMBOLS:

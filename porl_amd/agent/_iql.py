@@ -513,6 +513,45 @@ class IqlAgentBase(nn.Module):
                 ex.allreduce_stats_(eng.stats, first=1)
         sched.step()
 
+    def _no_backbone(self):
+        if getattr(self, "backbone", None) is not None:
+            raise NotImplementedError("evaluate with a backbone: DropPath and batch statistics make 'the parameters as they "
+                                      "stand' ambiguous in train mode; encode the rows yourself and score a head-only agent")
+
+    def _evaluate(self, obs, next_obs, rew, term, pol_target, replay=None, batch=None, idx=None):
+        """The two losses of the parameters AS THEY STAND on one minibatch, without taking a step:
+            target = r + (1 - d) * discount * min v_target(s'),   u_i = target - v_i(s)
+            v_loss = 1/2 sum_i mean(|tau - 1[u_i < 0]| * u_i^2)
+            g_loss = mean(w * nll),  w = the advantage weight from the CURRENT online twin (an update's policy phase sees
+                     the twin after its value step), nll of the current policy on the policy target.
+        Composition of existing phases — the value phase's forward + backward, the policy phase's forward half and its
+        backward, in which the loss partials are combined — with neither apply: no parameter, target net, Adam moment,
+        step count or schedule moves.  The gradient buffers, the workspace and the statistics buffer are scratch and ARE
+        overwritten (every update rewrites them before it reads them).  An outstanding pipelined policy phase is joined
+        first.  Under a data-parallel exchange the losses are this rank's over its own rows: no collective, and
+        inv_batch is 1 / the local batch.  `v_loss` is the number the next update on the same batch returns."""
+        self._no_backbone()
+        eng = self._engine
+        self.flush()
+        eng._ensure_bound()
+        eng.set_mode(0)                        # one staging slot, combines launched at once: nothing is left pending
+        B = self._load(obs, next_obs, rew, term, pol_target, replay, batch, idx)
+        hp = eng.hyper(tau=self.tau, discount=self.discount, alpha=self.alpha, ema_beta=self.beta, inv_batch=1.0 / B)
+        eng.value_backward(hp)                 # stats[0] = v_loss; the TD target stays in the workspace
+        eng.policy_forward(hp)                 # online twin again (head only), weights, NLL
+        eng.policy_backward(hp)                # its combine writes stats[1] = g_loss, stats[2] = min NLL
+        return B
+
+    def evaluate_from_replay(self, replay, batch_size, indices=None):
+        """`evaluate` on `batch_size` rows of a PackedReplay: drawn on the device as `update_from_replay` draws them
+        (`replay.draws` advances by one), or the local row numbers in `indices` (int64 device tensor; `replay.draws`
+        stays put).  -> (v_loss, g_loss), or the statistics view under `async_losses`.  Nothing of the agent moves; see
+        `evaluate`."""
+        self._no_backbone()
+        idx, _ = self._replay_rows(replay, batch_size, indices)
+        self._evaluate(None, None, None, None, None, replay=replay, batch=batch_size, idx=idx)
+        return self._losses()
+
     def _policy_loss(self):
         """g_loss of the last policy-only step: a float, or the stats[1:2] device view under async_losses."""
         if self.async_losses:
@@ -542,3 +581,42 @@ class IqlAgentBase(nn.Module):
                           "agent/por.py:104-105); continuing", RuntimeWarning)
         self.last_min_nll = min_nlp
         return v_loss, g_loss
+
+
+def evaluate_store(agent, store, batch_size=None):
+    """Mean losses of the agent's parameters as they stand over EVERY row of `store` (a PackedReplay, or anything with
+    `rows`, `obs_dim`, `act_dim` in its wire format) — e.g. the held-out part of `dataloader.holdout_region`.  The rows
+    are walked once, in order, in chunks of `batch_size` (default and at most the engine's `max_batch`; the last chunk may
+    be short), each scored like `evaluate_from_replay(store, n, indices=lo..hi)`; `loss * chunk_rows` is accumulated on
+    the device in fp64 and read back ONCE at the end.  -> {"v_loss", "g_loss", "min_nll", "n_rows"}: the row-weighted
+    means, the smallest per-row NLL, the row count.  Nothing of the agent moves (see `evaluate`); `store.draws` stays put.
+    With `async_losses` the result is still the dict of floats — the walk has to end in a read-back to be a mean.
+    Under a data-parallel exchange this is the local shard's mean.  Raises ValueError on an empty store or a NaN loss,
+    NotImplementedError with a backbone."""
+    agent._no_backbone()
+    eng = agent._engine
+    n = int(store.rows.shape[0])
+    if n < 1:
+        raise ValueError("evaluate_store: the store has no rows")
+    limit = eng.cfg.max_batch
+    chunk = limit if batch_size is None else int(batch_size)
+    if not 1 <= chunk <= limit:
+        raise RuntimeError(f"batch {chunk} outside [1, {limit}] (max_batch)")
+    dev = store.rows.device
+    acc = torch.zeros(2, dtype=torch.float64, device=dev)
+    low = torch.full((1,), float("inf"), dtype=torch.float32, device=dev)
+    for lo in range(0, n, chunk):
+        hi = min(n, lo + chunk)
+        idx, _ = agent._replay_rows(store, hi - lo, torch.arange(lo, hi, dtype=torch.int64, device=dev))
+        agent._evaluate(None, None, None, None, None, replay=store, batch=hi - lo, idx=idx)
+        acc.add_(eng.stats[:2].double(), alpha=float(hi - lo))
+        torch.minimum(low, eng.stats[2:3], out=low)
+    v_sum, g_sum, min_nll = torch.cat([acc, low.double()]).tolist()      # the one read-back
+    v_loss, g_loss = v_sum / n, g_sum / n
+    if math.isnan(v_loss) or math.isnan(g_loss):
+        raise ValueError("NaN loss: non-finite values in the store or the parameters")
+    if min_nll <= 0 and not IqlAgentBase._warned_nll:
+        IqlAgentBase._warned_nll = True
+        warnings.warn("per-sample NLL <= 0 in this store (the reference drops into pdb here, "
+                      "agent/por.py:104-105); continuing", RuntimeWarning)
+    return {"v_loss": v_loss, "g_loss": g_loss, "min_nll": min_nll, "n_rows": n}

@@ -23,7 +23,7 @@ import copy
 
 import torch
 
-from ._iql import ArenaAdam, CosineSchedule, IqlAgentBase
+from ._iql import ArenaAdam, CosineSchedule, IqlAgentBase, evaluate_store  # noqa: F401
 from .policy import GaussianPolicy
 from .value_functions import TwinV
 
@@ -70,6 +70,17 @@ class POR(IqlAgentBase):
             next_observations = agent.backbone(next_observations)
         return agent._full_update(observations, next_observations, rewards, terminals, target,
                                   agent.v_optimizer, agent.goal_policy_optimizer, agent.goal_lr_schedule)
+
+    def evaluate(agent, observations, next_observations, rewards, terminals):
+        """Extension (not in the reference): (v_loss, g_loss) of the parameters as they stand on this batch, WITHOUT a
+        step — the loss of `por_residual_update`'s value phase, and the goal policy's weighted NLL on s' with the
+        weight min(exp(adv / alpha), 100) taken from the current online twin.  Every parameter, the target nets, both
+        Adam moments and step counts and the cosine schedule stay bit for bit; an outstanding pipelined phase is
+        flushed first; gradient buffers, workspace and the statistics buffer are scratch.  With `async_losses` the
+        statistics view is returned, as by the update calls.  Under a data-parallel exchange the losses are this rank's
+        own.  With a backbone: NotImplementedError.  `evaluate_from_replay` / `evaluate_store` score rows of a store."""
+        agent._evaluate(observations, next_observations, rewards, terminals, next_observations)
+        return agent._losses()
 
     def update_from_replay(agent, replay, batch_size, indices=None):
         """Extension (not in the reference): one POR step on `batch_size` distinct rows drawn on the device

@@ -22,7 +22,7 @@ import copy
 
 import torch
 
-from ._iql import ArenaAdam, CosineSchedule, IqlAgentBase
+from ._iql import ArenaAdam, CosineSchedule, IqlAgentBase, evaluate_store  # noqa: F401
 from .policy import BoundedGaussianPolicy
 from .value_functions import TwinV
 
@@ -74,6 +74,17 @@ class SORL(IqlAgentBase):
             next_observations = agent.backbone(next_observations)
         return agent._full_update(observations, next_observations, rewards, terminals, actions,
                                   agent.v_optimizer, agent.policy_optimizer, agent.lr_schedule)
+
+    def evaluate(agent, observations, actions, rewards, next_observations, terminals):
+        """Extension (not in the reference): (v_loss, g_loss) of the parameters as they stand on this batch, WITHOUT a
+        step — the loss of `update`'s value phase, and the policy's weighted NLL on the actions with the weight
+        min(exp(alpha * adv), 100) taken from the current online twin.  Every parameter, the target nets, both Adam
+        moments and step counts and the cosine schedule stay bit for bit; an outstanding pipelined phase is flushed
+        first; gradient buffers, workspace and the statistics buffer are scratch.  With `async_losses` the statistics
+        view is returned, as by the update calls.  Under a data-parallel exchange the losses are this rank's own.  With
+        a backbone: NotImplementedError.  `evaluate_from_replay` / `evaluate_store` score rows of a store."""
+        agent._evaluate(observations, next_observations, rewards, terminals, actions)
+        return agent._losses()
 
     def vf_update(agent, observations, actions, rewards, next_observations, terminals):
         """Value step only (reference sorl.py:130-152) -> v_loss."""

@@ -25,6 +25,7 @@
 #include "bcq_mask.hpp"
 #include "astar.hpp"
 #include "episodes.hpp"
+#include "partition.hpp"
 
 using namespace porl;
 
@@ -2013,3 +2014,4 @@ int porl_prof_read(porl_prof_entry* out, int max_entries) {
 #include "encoder_api.inc"
 #include "iqn_api.inc"
 #include "episodes_api.inc"
+#include "partition_api.inc"

@@ -89,3 +89,10 @@ def rvs_sample_batch(dataset, batch_size):
     porl_amd.dataloader.episodes.rvs_sample_batch."""
     from ..dataloader import episodes
     return episodes.rvs_sample_batch(dataset, batch_size)
+
+
+def generate_test_generlaization_data(dataset, env_name, env_idx=None):
+    """Delete the transitions inside the hold-out box of `env_name` (reference util/util.py:219-238, its spelling), on
+    the device: porl_amd.dataloader.holdout.generate_test_generlaization_data."""
+    from ..dataloader import holdout
+    return holdout.generate_test_generlaization_data(dataset, env_name, env_idx)
