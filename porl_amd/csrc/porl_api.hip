@@ -1417,6 +1417,19 @@ static int pack_x(porl_iql* h, const float* x, int64_t x_rs, int batch, int64_t 
   return PORL_OK;
 }
 
+// The small-batch path stages the B x K input of every layer in LDS (K = obs_dim, then hidden_dim): whether the whole
+// layer chain fits is decided before its first launch, and a chain that does not takes the batched path instead.
+constexpr size_t SMALL_FWD_LDS_BYTES = 64 * 1024;
+static bool small_fwd_fits(const porl_iql* h, int batch) {
+  return batch >= 1 && batch <= SMALL_FWD_MAX_B &&
+         sizeof(float) * (size_t)batch * std::max(h->cfg.obs_dim, h->cfg.hidden_dim) <= SMALL_FWD_LDS_BYTES;
+}
+static int check_forward_batch(const porl_iql* h, int batch) {
+  // both paths write `batch` rows of scratch sized for max_batch rows
+  if (batch < 1 || batch > h->cfg.max_batch) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", batch, h->cfg.max_batch);
+  return PORL_OK;
+}
+
 // One Linear layer of up to 2 networks on a handful of rows (kernels.hpp: small_fwd_kernel).
 static int small_fwd(int nnets, const float* const* Wt, const float* const* bias, const float* const* X, const long* ldx,
                      float* const* Y, const long* ldy, int N, int K, int B, int act, hipStream_t s) {
@@ -1424,7 +1437,7 @@ static int small_fwd(int nnets, const float* const* Wt, const float* const* bias
   for (int i = 0; i < nnets; ++i) { a.W[i] = Wt[i]; a.bias[i] = bias[i]; a.X[i] = X[i]; a.ldx[i] = ldx[i]; a.Y[i] = Y[i]; a.ldy[i] = ldy[i]; }
   a.N = N; a.K = K; a.B = B; a.act = act;
   const size_t lds = sizeof(float) * (size_t)B * K;
-  if (lds > 64 * 1024) PORL_FAIL(PORL_ERR_UNSUPPORTED, "small-batch path: B*K too large");
+  if (lds > SMALL_FWD_LDS_BYTES) PORL_FAIL(PORL_ERR_UNSUPPORTED, "small-batch path: B*K too large");
   ProfScope ps("small_fwd_kernel", s, 2.0 * nnets * B * N * K, 4.0 * nnets * ((double)N * K + B * (N + K)));
   hipLaunchKernelGGL(small_fwd_kernel, dim3(std::min(cdiv(N, 4), 1024), nnets), dim3(256), lds, s, a);
   PORL_HIP(hipGetLastError());
@@ -1435,8 +1448,9 @@ int porl_iql_forward_value(porl_iql* h, int which, const float* x, int64_t x_rs,
                            float* v2_out, void* stream) {
   PORL_TRY(check_ready(h, false)); DevGuard _dg(h->device);
   if (!v1_out || !v2_out) PORL_FAIL(PORL_ERR_INVALID, "null output");
+  PORL_TRY(check_forward_batch(h, batch));
   hipStream_t s = (hipStream_t)stream;
-  if (batch >= 1 && batch <= SMALL_FWD_MAX_B && !h->cfg.layer_norm && x) {
+  if (small_fwd_fits(h, batch) && !h->cfg.layer_norm && x) {
     // inference-sized batch: 3 GEMV launches straight from the caller's rows (no staging copy, no split-K)
     const int S = h->cfg.obs_dim, H = h->cfg.hidden_dim, L = h->cfg.n_hidden;
     float* W = h->buf.workspace;
@@ -1488,8 +1502,9 @@ int porl_iql_forward_policy(porl_iql* h, const float* x, int64_t x_rs, int32_t b
                             int64_t mean_rs, void* stream) {
   PORL_TRY(check_ready(h, false)); DevGuard _dg(h->device);
   if (!mean_out) PORL_FAIL(PORL_ERR_INVALID, "null output");
+  PORL_TRY(check_forward_batch(h, batch));
   hipStream_t s = (hipStream_t)stream;
-  if (batch >= 1 && batch <= SMALL_FWD_MAX_B && x) {
+  if (small_fwd_fits(h, batch) && x) {
     const int S = h->cfg.obs_dim, H = h->cfg.hidden_dim, L = h->cfg.n_hidden, D = h->cfg.pol_out_dim;
     float* W = h->buf.workspace;
     const float* P = h->buf.params_pol;

@@ -359,7 +359,8 @@ class IqlEngine:
         """Rollout path (reference test.py:28-30: one observation in, one action out as numpy): the three small-batch
         launches read the observation from and write the mean to PINNED HOST memory — no copy launches, no torch
         kernels, one stream synchronisation.  `x`: (B <= 8, obs_dim) float32, a device tensor, a CPU tensor or an
-        ndarray.  Returns a fresh (B, D) float32 ndarray."""
+        ndarray.  Returns a fresh (B, D) float32 ndarray.  Rows too wide for the small-batch kernels (more than
+        64 KiB for the B inputs of a layer) take the batched path, which reads and writes the same pinned buffers."""
         self._ensure_bound()
         self.join()
         B, D, S = int(x.shape[0]), self.cfg.pol_out_dim, self.cfg.obs_dim

@@ -18,6 +18,12 @@ static int g_checks = 0, g_bad = 0;
     if (_r == 0) { ++g_bad; std::fprintf(stderr, "accepted: %s\n", #expr); }                  \
     else if (!porl_last_error() || !porl_last_error()[0]) { ++g_bad; std::fprintf(stderr, "no message: %s\n", #expr); } \
   } while (0)
+// a rejection for the stated reason: the message must contain `what`
+#define REJECT_MSG(expr, what)                                                                \
+  do {                                                                                        \
+    REJECT(expr);                                                                             \
+    if (!std::strstr(porl_last_error(), what)) { ++g_bad; std::fprintf(stderr, "wrong reason (%s): %s\n", porl_last_error(), #expr); } \
+  } while (0)
 #define ACCEPT(expr)                                                                          \
   do {                                                                                        \
     ++g_checks;                                                                               \
@@ -93,6 +99,22 @@ int main() {
   REJECT(porl_iql_step(h, &hp, nullptr));
   REJECT(porl_iql_forward_value(h, 0, nullptr, 60, 4, x, x, nullptr));
   REJECT(porl_iql_forward_policy(h, x, 60, 100000, x, 60, nullptr));
+  REJECT_MSG(porl_iql_forward_value(h, 0, x, 60, 0, x, x, nullptr), "outside [1,128]");
+  REJECT_MSG(porl_iql_forward_policy(h, x, 60, 129, x, 60, nullptr), "outside [1,128]");
+  {
+    // a batch the small-batch path would take (<= 8 rows) on an engine whose scratch holds fewer rows: refused by the
+    // range check, before either path is chosen
+    porl_iql* h4 = nullptr;
+    porl_iql_cfg c4 = c;
+    c4.max_batch = 4;
+    ACCEPT(porl_iql_create(&c4, &h4));
+    if (porl_iql_group_floats(h4, 0) != nv || porl_iql_workspace_floats(h4) > nw) ++g_bad;    // the buffers above are large enough
+    ACCEPT(porl_iql_bind(h4, &bufs));
+    REJECT_MSG(porl_iql_forward_value(h4, 0, x, 60, 8, x, x, nullptr), "outside [1,4]");
+    REJECT_MSG(porl_iql_forward_value(h4, 1, x, 60, 5, x, x, nullptr), "outside [1,4]");
+    REJECT_MSG(porl_iql_forward_policy(h4, x, 60, 8, x, 60, nullptr), "outside [1,4]");
+    porl_iql_destroy(h4);
+  }
   {
     void* s1 = reinterpret_cast<void*>(0x10); void* s2 = reinterpret_cast<void*>(0x20);
     REJECT(porl_iql_update_pipelined(h, &hp, 32, x, 124, 1000, 2, 0, 1, 0, nullptr, nullptr, nullptr, 1, 0, 0, 1, s1, s2));   // no signals
