@@ -126,6 +126,46 @@ int main() {
     REJECT(porl_iql_update_pipelined(h, &hp, 32, x, 124, (int64_t)1 << 41, 2, 0, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2));         // n_rows > 2^40
     REJECT(porl_iql_update_pipelined(h, nullptr, 32, x, 124, 1000, 2, 0, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2));
   }
+  {
+    // The checks every IQL entry point shares (csrc/iql_api.inc: iql_enter, check_batch, check_replay_rows), each for its
+    // stated reason.  What a program can see of the engine's state without a GPU is whether a minibatch counts as loaded:
+    // after every rejection the value phase must still refuse for want of one (TWO_SLOTS is on: a loader that moved the
+    // staging slot before refusing would not show here, only in the launch records of tests/test_iql_launches_gpu.py).
+    void* s1 = reinterpret_cast<void*>(0x10); void* s2 = reinterpret_cast<void*>(0x20);
+    int64_t idx[8] = {0};
+#define REJECT_UNTOUCHED(expr, what)                                                          \
+  do {                                                                                        \
+    REJECT_MSG(expr, what);                                                                   \
+    REJECT_MSG(porl_iql_value_backward(h, &hp, nullptr), "no minibatch loaded");              \
+  } while (0)
+    // null hyper-parameters: named where no minibatch is needed; behind the missing minibatch everywhere else
+    REJECT_UNTOUCHED(porl_iql_value_apply(h, nullptr, nullptr), "null hyper-parameters");
+    REJECT_UNTOUCHED(porl_iql_policy_apply(h, nullptr, nullptr), "null hyper-parameters");
+    REJECT_UNTOUCHED(porl_iql_update_pipelined(h, nullptr, 32, x, 124, 1000, 2, 0, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2), "null hyper-parameters");
+    REJECT_MSG(porl_iql_value_backward(h, nullptr, nullptr), "no minibatch loaded");
+    REJECT_MSG(porl_iql_policy_forward(h, nullptr, nullptr), "no minibatch loaded");
+    REJECT_MSG(porl_iql_policy_backward(h, nullptr, nullptr), "no minibatch loaded");
+    REJECT_MSG(porl_iql_step(h, nullptr, nullptr), "no minibatch loaded");
+    REJECT_MSG(porl_iql_policy_only_forward(h, nullptr, nullptr), "no minibatch loaded");
+    REJECT_MSG(porl_iql_policy_only_step(h, nullptr, nullptr), "no minibatch loaded");
+    REJECT_MSG(porl_iql_policy_prefetch(h, nullptr), "no minibatch loaded");
+    // one row more than the workspace holds: the three loaders and the one-call update
+    REJECT_UNTOUCHED(porl_iql_load_batch(h, 129, x, 60, x, 60, x, 1, x, 1, x, 60, nullptr), "outside [1,128]");
+    REJECT_UNTOUCHED(porl_iql_load_batch_sampled(h, 129, x, 124, 1000, 2, 0, 1, 0, nullptr, nullptr), "outside [1,128]");
+    REJECT_UNTOUCHED(porl_iql_load_batch_indexed(h, 129, x, 124, 1000, idx, 60, 2, 0, 0, nullptr, 0, nullptr, 0, nullptr), "outside [1,128]");
+    REJECT_UNTOUCHED(porl_iql_update_pipelined(h, &hp, 129, x, 124, 1000, 2, 0, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2), "outside [1,128]");
+    // the replay-row checks, the same for the sampled loader and the one-call update that draws through it
+    REJECT_UNTOUCHED(porl_iql_load_batch_sampled(h, 32, x, 124, 31, 2, 0, 1, 0, nullptr, nullptr), "replay rows");
+    REJECT_UNTOUCHED(porl_iql_update_pipelined(h, &hp, 32, x, 124, 31, 2, 0, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2), "replay rows");
+    REJECT_UNTOUCHED(porl_iql_update_pipelined(h, &hp, 32, nullptr, 124, 1000, 2, 0, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2), "replay rows");
+    REJECT_UNTOUCHED(porl_iql_load_batch_sampled(h, 32, x, 123, 1000, 2, 0, 1, 0, nullptr, nullptr), "row stride");
+    REJECT_UNTOUCHED(porl_iql_update_pipelined(h, &hp, 32, x, 123, 1000, 2, 0, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2), "row stride");
+    REJECT_UNTOUCHED(porl_iql_load_batch_sampled(h, 32, x, 124, 1000, -1, 0, 1, 0, nullptr, nullptr), "row stride");
+    REJECT_UNTOUCHED(porl_iql_update_pipelined(h, &hp, 32, x, 124, 1000, -1, 0, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2), "row stride");
+    REJECT_UNTOUCHED(porl_iql_update_pipelined(h, &hp, 32, x, 124, 1000, 2, 1, 1, 0, x, x, x, 1, 0, 0, 1, s1, s2), "policy target width");
+    REJECT_UNTOUCHED(porl_iql_load_batch_sampled(h, 32, x, 124, 1000, 2, 1, 1, 0, nullptr, nullptr), "policy target width");
+#undef REJECT_UNTOUCHED
+  }
   REJECT(porl_iql_tune_set(h, "no_such_key", 1));
   REJECT(porl_iql_tune_set(h, nullptr, 1));
   ACCEPT(porl_iql_tune_set(h, "skinny", 0));

@@ -52,9 +52,9 @@ BY_NAME = {c.name: c for c in CASES}
 ALLOWED_BATCHES = (1, 2, 7, 8, 9, 63, 64, 65, 130)
 X_ROWS = max(ALLOWED_BATCHES)
 
-# ---- the host code's choice of launches (porl_api.hip), restated --------------------------------------------------
+# ---- the host code's choice of launches (iql_api.inc), restated --------------------------------------------------
 SMALL_FWD_MAX_B = 8                    # kernels.hpp
-SMALL_FWD_LDS_BYTES = 64 * 1024        # porl_api.hip: B x K floats of a layer's input are staged in LDS
+SMALL_FWD_LDS_BYTES = 64 * 1024        # iql_api.inc: B x K floats of a layer's input are staged in LDS
 L0_KP, SKN_T = 64, 64                  # l0_fwd.hpp, skinny.hpp
 SMALL, L0, SKINNY, GEMM, LN = ("small_fwd_kernel", "l0_fwd_kernel", "mean_skinny_kernel", "gemm_f32_kernel",
                                "ln_relu_fwd_kernel")
