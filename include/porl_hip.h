@@ -748,6 +748,44 @@ int porl_partition_rows(const void* rows, int64_t stride_bytes, int64_t n_rows, 
                         const porl_partition_box* box, void* out, int64_t* index, int64_t* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Column statistics and the affine column pass of a resident store (kernels in csrc/colstats.hpp): what the reference's
+ * `--normalize` (por_train.py:141) takes from a dataset — mean / std of the observation columns, obs = (obs - mean) / std
+ * (util/util.py:146,160,177) — and the reward rescaling r /= (max_ret - min_ret); r *= max_episode_steps that return_range
+ * (util/util.py:67-80) exists for.  Rows are fp32 and read in place through (rows, stride_floats, n_rows): a dense store,
+ * a row-strided view or a column block of a wider one.  The statistics never write their input; they accumulate in fp64
+ * and combine partial results only by the pairwise update d = mean_b - mean_a, mean = mean_a + d n_b / n,
+ * M2 = M2_a + M2_b + d^2 n_a n_b / n (with the rounding residual of every partial mean carried along), in an order that follows from n_rows, n_cols and the two tile constants alone: no
+ * floating-point atomics, no block waits on another, two calls on equal values (dense or strided) return equal bits, a
+ * constant column has M2 == 0.0 exactly, a column holding a NaN has NaN in all four results.
+ * --------------------------------------------------------------------------------------------- */
+/* doubles of workspace for n_rows x n_cols; -1 when out of range.  Also reports the tile constants
+ * (rows per block, partials per sweep); either pointer may be null. */
+int64_t porl_colstats_workspace(int64_t n_rows, int32_t n_cols, int32_t* rows_per_block, int32_t* partials_per_sweep);
+
+/* out = [mean(C) | M2(C) | min(C) | max(C)], fp64, C = n_cols.  Columns [col0, col0 + n_cols) of an fp32 row view are read
+ * in place through (rows, stride_floats, n_rows).  M2 = sum (x - mean)^2.  The input is never written.  n_rows in
+ * [1, 2^36], n_cols in [1, 4096], col0 + n_cols <= stride_floats <= 2^20.  One launch over the rows (16-byte lanes when
+ * rows + col0, stride_floats and n_cols allow, else 4-byte lanes; same result either way), then one launch per merge
+ * level.  The caller reads `out` back — the only synchronisation. */
+int porl_col_stats(const float* rows, int64_t stride_floats, int64_t n_rows, int32_t col0, int32_t n_cols,
+                   double* workspace, double* out, void* stream);
+
+typedef struct porl_col_span { int32_t col0, n_cols, param0, flags; } porl_col_span;   /* flags bit 0: multiply */
+
+/* for every span and j < n_cols:
+ *   out[i, col0+j] = fl( fl(rows[i, col0+j] - shift[param0+j]) / div[param0+j] )
+ * then, if flags&1, fl( . * mul[param0+j] ): three IEEE round-to-nearest fp32 operations, never fused, the quotient
+ * never a multiplication by a reciprocal.  Columns outside the spans are not touched (neither loaded nor stored).
+ * `spans` is a HOST array, 1..8 entries, validated before any device call: every span inside `width` and inside
+ * n_params, no two overlapping; mul may be null only if no span has bit 0 set.  shift / div / mul are device vectors
+ * of n_params floats.  out may be rows itself (in place, then with the same stride: every element is read and written
+ * once, by the same lane) or another buffer of at least `width` columns that does not otherwise overlap rows.
+ * width <= stride_floats, out_stride_floats <= 2^20.  One launch. */
+int porl_affine_cols(const float* rows, int64_t stride_floats, int64_t n_rows, int32_t width,
+                     const porl_col_span* spans, int32_t n_spans, const float* shift, const float* div,
+                     const float* mul, int32_t n_params, float* out, int64_t out_stride_floats, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Costmap encoder engine: FasterNet.forward_cls (agent/fasternet.py:428-438) as built by
  * sorl_train.py:29 `FasterNet(3, args.feature_dim)` — state2costmap, PatchEmbed 4x4s4 + BN (:234-246),
  * depth0 MLPBlocks (:141-194, Partial_conv3 :110-138), PatchMerging 2x2s2 + BN (:249-261), depth1

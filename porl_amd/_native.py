@@ -40,6 +40,7 @@ SYMBOLS = [
     "porl_episode_workspace", "porl_episode_count", "porl_episode_fill", "porl_episode_returns", "porl_hindsight_pairs",
     "porl_gather_pairs",
     "porl_partition_workspace", "porl_partition_mask", "porl_partition_rows",
+    "porl_colstats_workspace", "porl_col_stats", "porl_affine_cols",
 ]
 
 
@@ -138,6 +139,10 @@ class AstarParams(C.Structure):
 
 class PartitionBox(C.Structure):
     _fields_ = [("cx", C.c_int32), ("cy", C.c_int32)] + [(n, C.c_float) for n in ("x_lo", "x_hi", "y_lo", "y_hi")]
+
+
+class ColSpan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("col0", "n_cols", "param0", "flags")]      # flags bit 0: multiply
 
 
 class ProfEntry(C.Structure):
@@ -291,6 +296,10 @@ def _declare(lib):
     lib.porl_partition_workspace.restype = i64
     lib.porl_partition_mask.argtypes = [vp, i64, i64, i64, C.POINTER(PartitionBox), vp, vp]
     lib.porl_partition_rows.argtypes = [vp, i64, i64, i64, vp, C.POINTER(PartitionBox), vp, vp, vp, vp]
+    lib.porl_colstats_workspace.argtypes = [i64, i32, C.POINTER(i32), C.POINTER(i32)]
+    lib.porl_colstats_workspace.restype = i64
+    lib.porl_col_stats.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp]
+    lib.porl_affine_cols.argtypes = [vp, i64, i64, i32, C.POINTER(ColSpan), i32, vp, vp, vp, i32, vp, i64, vp]
     lib.porl_prof_enable.argtypes = [C.c_int]
     lib.porl_prof_read.argtypes = [C.POINTER(ProfEntry), C.c_int]
     for name in SYMBOLS:

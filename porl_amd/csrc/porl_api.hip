@@ -26,6 +26,7 @@
 #include "astar.hpp"
 #include "episodes.hpp"
 #include "partition.hpp"
+#include "colstats.hpp"
 
 using namespace porl;
 
@@ -858,3 +859,4 @@ int porl_prof_read(porl_prof_entry* out, int max_entries) {
 #include "iqn_api.inc"
 #include "episodes_api.inc"
 #include "partition_api.inc"
+#include "colstats_api.inc"

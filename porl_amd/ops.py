@@ -67,6 +67,10 @@ SCHEMAS = {
     "astar_label": "(Tensor rows, float resolution=0.1, float robot_radius=0.13, float min_x=-10., float max_x=10., "
                    "float min_y=-5., float max_y=5., float range_lo=0.15, float range_hi=3.5, int n_beams=360, "
                    "int pose_offset=360, int heading_offset=362, int goal_offset=363) -> (Tensor, Tensor, Tensor)",
+    # fp64 [mean | M2 | min | max] (4, n_cols) of columns [col0, col0 + n_cols) of fp32 rows, read in place
+    "col_stats": "(Tensor rows, int col0, int n_cols) -> Tensor",
+    # rows[:, c0+j] = fl(fl(rows[:, c0+j] - shift[p0+j]) / div[p0+j]) [* mul[p0+j]] in place; spans = (c0, n_cols, p0, flags)*
+    "affine_cols": "(Tensor(a!) rows, int[] spans, Tensor shift, Tensor div, Tensor? mul) -> ()",
 }
 for _name, _schema in SCHEMAS.items():
     LIB.define(_name + _schema)
@@ -173,9 +177,23 @@ def _astar_label(rows, resolution=0.1, robot_radius=0.13, min_x=-10., max_x=10.,
                         heading_offset=heading_offset, goal_offset=goal_offset)
 
 
+def _col_stats(rows, col0, n_cols):
+    from .dataloader.normalize import _as_rows, col_stats_device
+    return col_stats_device(_as_rows(rows), col0, n_cols)
+
+
+def _affine_cols(rows, spans, shift, div, mul):
+    from .dataloader.normalize import _as_rows, affine_cols_device
+    _need_cuda(shift, div, mul)
+    if len(spans) % 4:
+        raise RuntimeError("affine_cols: spans is a flat list of (col0, n_cols, param0, flags)")
+    affine_cols_device(_as_rows(rows), [tuple(spans[i:i + 4]) for i in range(0, len(spans), 4)], shift, div, mul)
+
+
 _IMPLS = dict(por_step=_por_step, iql_value_step=_iql_value_step, awr_policy_step=_awr_policy_step, cql_step=_cql_step,
               replay_gather=_replay_gather, adam_ema_sweep=_adam_ema_sweep, mlp_forward=_mlp_forward, gemm_f32=_gemm_f32,
-              sample_indices=_sample_indices, state2costmap=_state2costmap, astar_label=_astar_label)
+              sample_indices=_sample_indices, state2costmap=_state2costmap, astar_label=_astar_label,
+              col_stats=_col_stats, affine_cols=_affine_cols)
 
 
 def _no_cpu(name):

@@ -6,6 +6,7 @@ device arithmetic is done by the HIP engine (porl_amd/engine.py), never by torch
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -96,3 +97,72 @@ def generate_test_generlaization_data(dataset, env_name, env_idx=None):
     the device: porl_amd.dataloader.holdout.generate_test_generlaization_data."""
     from ..dataloader import holdout
     return holdout.generate_test_generlaization_data(dataset, env_name, env_idx)
+
+
+def torchify(x, device):
+    """A host array as a tensor on `device`, fp64 narrowed to fp32 (the reference's helper of this name, util/util.py:59-64,
+    sends it to a global `DEFAULT_DEVICE` that it never defines; the evaluators below pass the policy's device)."""
+    t = torch.as_tensor(np.asarray(x))
+    return t.to(device=device, dtype=torch.float32 if t.dtype == torch.float64 else t.dtype)
+
+
+def _host_stats(what, mean, std, nets):
+    """(mean, std) as host arrays and the device of `nets`.  `mean` may be a dataloader.Normalizer, which carries both
+    (`std` is then ignored).  There is no CPU path: a network on the host raises NativeError."""
+    from .. import _native as N
+    from ..dataloader.normalize import Normalizer
+    devices = [next(net.parameters()).device for net in nets]
+    for d in devices:
+        if d.type != "cuda":
+            raise N.NativeError(f"{what}: the policy is on {d}, policy.act runs on a HIP device only (no CPU path)")
+    if isinstance(mean, Normalizer):
+        mean, std = mean.numpy()
+    elif std is None:
+        raise TypeError(f"{what}: std is required unless mean is a Normalizer")
+    return np.asarray(mean), np.asarray(std), devices[0]
+
+
+def _rollout(env, policy, mean, std, device, deterministic, begin):
+    """One episode, the sum of its rewards.  Per step, in the reference's order (util/util.py:141-185): the observation
+    is normalised in numpy on the host, `step_input` turns it into the policy's input, the policy acts on the device
+    and the environment (four return values) takes the action.  `begin(act)` runs once after `env.reset()` and returns
+    `step_input`; `act(net, x)` is a network's action for the host vector `x`, back on the host."""
+    def act(net, x):
+        with torch.no_grad():
+            return net.act(torchify(x, device), deterministic=deterministic).cpu().numpy()
+
+    raw = env.reset()
+    step_input = begin(act)
+    episode_return, finished = 0.0, False
+    while not finished:
+        raw, reward, finished, _ = env.step(act(policy, step_input((raw - mean) / std)))
+        episode_return += reward
+    return episode_return
+
+
+def evaluate_iql(env, policy, mean, std=None, deterministic=True):
+    """Return of one episode of `policy` on normalised observations.  `mean, std` are numpy arrays, or `mean` is a
+    dataloader.Normalizer."""
+    mean, std, device = _host_stats("evaluate_iql", mean, std, (policy,))
+    return _rollout(env, policy, mean, std, device, deterministic, lambda act: lambda z: z)
+
+
+def evaluate_por(env, policy, goal_policy, mean, std=None, deterministic=True):
+    """Return of one episode in which `goal_policy` proposes a goal from the normalised observation and `policy` acts on
+    [observation | goal]."""
+    mean, std, device = _host_stats("evaluate_por", mean, std, (policy, goal_policy))
+    return _rollout(env, policy, mean, std, device, deterministic,
+                    lambda act: lambda z: np.concatenate([z, act(goal_policy, z)]))
+
+
+def evaluate_rvs(env, policy, mean, std=None, deterministic=True):
+    """Return of one episode in which `policy` acts on [observation | goal]: the goal is `env.target_goal`, read once
+    after the reset and normalised by the first two entries of `mean, std`.  The reference's progress print is left
+    out."""
+    mean, std, device = _host_stats("evaluate_rvs", mean, std, (policy,))
+
+    def begin(act):
+        goal = (np.asarray(env.target_goal) - mean[:2]) / std[:2]
+        return lambda z: np.concatenate([z, goal])
+
+    return _rollout(env, policy, mean, std, device, deterministic, begin)
