@@ -207,7 +207,11 @@ int porl_iql_forward_policy(porl_iql* h, const float* x, int64_t x_rs, int32_t b
  * --------------------------------------------------------------------------------------------- */
 typedef struct porl_qnet_cfg {
   int32_t state_dim;
-  int32_t n_actions;                 /* <= 64 */
+  int32_t n_actions;                 /* outputs, <= 4096.  Up to 128 outputs (and every other width <= 128, <= 5 Linear
+                                      * layers, the LDS plan fits: porl_qnet_one_launch) the learn step runs on the
+                                      * one-launch kernels; wider output layers take the multi-launch path.  Both are
+                                      * tested per row against an fp64 step up to 128 outputs, the multi-launch path at
+                                      * 129 as well (tests/test_qstep_gpu.py). */
   int32_t n_hidden;                  /* QNetwork default: 3 */
   int32_t hidden[PORL_MAX_HIDDEN];   /* QNetwork default: 64, 128, 64 */
   int32_t max_batch;

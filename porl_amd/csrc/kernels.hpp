@@ -1009,7 +1009,8 @@ __global__ __launch_bounds__(256) void ln_relu_bwd_kernel(const LnBwdArgs a) {
 //   y = r + gamma * max_a Q_tgt(s', a) * (1 - d);  td = mean((Q(s)[a] - y)^2)
 //   pen = mean(logsumexp_a Q(s, a) - ln A - Q(s)[a]);  loss = td + alpha * pen
 //   dL/dQ[b, j] = alpha/B * softmax_j + 1[j == a] * (2/B (Q[a] - y) - alpha/B)
-// One thread per row (A <= 64), per-block partial sums, fixed-order finalize.
+// One thread per row (run-time loops over the A outputs: any A the engine accepts), per-block partial sums,
+// fixed-order finalize.
 // ---------------------------------------------------------------------------------------------------
 struct CqlLossArgs {
   const float* Q; const float* Qn; int ldq;

@@ -177,7 +177,7 @@ def test_one_launch_gradients_on_odd_shapes(S, A, B, hidden):
 
 
 @pytest.mark.parametrize("S,A,B,hidden", [(60, 10, 4096, (64, 128, 64)), (17, 3, 33, (32, 96)), (5, 2, 1, (7,)), (12, 5, 100, (64,))])
-@pytest.mark.parametrize("variant", ["cql", "double_dqn", "bcq_mask"])
+@pytest.mark.parametrize("variant", ["cql", "double_dqn", "bcq_mask", "both_weights", "td_off"])
 def test_two_group_step_kernel_is_bit_identical_to_the_one_group_kernel(S, A, B, hidden, variant):
     """csrc/qnet_fused.hpp: the 512-thread kernel (target net || online net, dZ chain || dW tiles on two wave groups)
     performs the same arithmetic in the same summation orders as the 256-thread kernel: three learn steps on indexed
@@ -194,6 +194,8 @@ def test_two_group_step_kernel_is_bit_identical_to_the_one_group_kernel(S, A, B,
     init = [rng.uniform(-0.3, 0.3, 200_000).astype(np.float32) for _ in range(2)]
     mask = torch.from_numpy((rng.uniform(size=(B, A)) < 0.6).astype(np.float32)).to(DEV)
     idxs = [torch.from_numpy(rng.permutation(N)[:B].astype(np.int64)).to(DEV) for _ in range(3)]
+    is_w = torch.from_numpy(rng.uniform(0.2, 1.0, B).astype(np.float32)).to(DEV)      # (drawn last: the older variants' inputs stay)
+    w_uniform = torch.tensor([0.37], dtype=torch.float32, device=DEV)
     out = []
     for two, rows16 in ((1, 0), (0, 0), (1, 1)):
         try:
@@ -212,6 +214,10 @@ def test_two_group_step_kernel_is_bit_identical_to_the_one_group_kernel(S, A, B,
                 var = NN.QnetVariant(1, None, None, NN.ptr(td_abs), None, 0)
             elif variant == "bcq_mask":
                 var = NN.QnetVariant(0, None, None, NN.ptr(td_abs), NN.ptr(mask), 0)
+            elif variant == "both_weights":
+                var = NN.QnetVariant(0, NN.ptr(is_w), NN.ptr(w_uniform), NN.ptr(td_abs), None, 0)
+            elif variant == "td_off":
+                var = NN.QnetVariant(0, None, None, NN.ptr(td_abs), None, 1)
             for k in range(3):
                 hp = eng.hyper(0.99, 0.7, 1.0 / B, k + 1, 5e-4)
                 eng.learn_indexed(hp, st_d, ac_d, rw_d, ns_d, dn_d, idxs[k], variant=var)
