@@ -73,13 +73,14 @@ def quantile_huber(cur, td, taus, kappa):
 
 
 class IqnOracle:
-    def __init__(self, P, P_target, gamma, kappa, lr=5e-4, max_norm=10.0, dtype=np.float64):
-        self.P = {k: np.asarray(v, dtype=dtype).copy() for k, v in P.items()}
-        self.T = {k: np.asarray(v, dtype=dtype).copy() for k, v in P_target.items()}
+    def __init__(self, P, P_target, gamma, kappa, lr=5e-4, max_norm=10.0, dtype=np.float64, m=None, v=None, t=0):
+        """m, v, t: Adam moments and the number of steps already taken (a run in progress); a fresh optimizer by default"""
+        self.P = {k: np.asarray(v_, dtype=dtype).copy() for k, v_ in P.items()}
+        self.T = {k: np.asarray(v_, dtype=dtype).copy() for k, v_ in P_target.items()}
         self.gamma, self.kappa, self.lr, self.max_norm, self.dtype = gamma, kappa, lr, max_norm, dtype
-        self.m = {k: np.zeros_like(v) for k, v in self.P.items()}
-        self.v = {k: np.zeros_like(v) for k, v in self.P.items()}
-        self.t = 0
+        self.m = {k: np.zeros_like(p) if m is None else np.asarray(m[k], dtype=dtype).copy() for k, p in self.P.items()}
+        self.v = {k: np.zeros_like(p) if v is None else np.asarray(v[k], dtype=dtype).copy() for k, p in self.P.items()}
+        self.t = int(t)
 
     def learn(self, states, actions, rewards, next_states, dones, taus_p, taus_pp):
         """iqn_trainer.py:92-134 -> loss"""
@@ -108,6 +109,6 @@ class IqnOracle:
             mh = self.m[k] / (1 - b1 ** self.t)
             vh = self.v[k] / (1 - b2 ** self.t)
             self.P[k] = self.P[k] - self.lr * mh / (np.sqrt(vh) + eps)
-        self.grad_norm = total
+        self.grad_norm, self.coef, self.a_star = total, coef, a_star
         self.G = {k: G[k] * coef for k in G}             # what the optimizer saw (after clipping)
         return float(loss)

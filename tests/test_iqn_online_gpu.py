@@ -75,7 +75,9 @@ def _head(zc, zo, zt, act, r, d, taus, gamma, kappa, ld=None):
 
 
 @pytest.mark.parametrize("kappa", [0.5, 1.0])
-@pytest.mark.parametrize("B,NP,NPP,A", [(6, 4, 4, 3), (37, 3, 5, 2), (1, 1, 1, 3), (3, 70, 9, 4)])
+@pytest.mark.parametrize("B,NP,NPP,A", [(6, 4, 4, 3), (37, 3, 5, 2), (1, 1, 1, 3), (3, 70, 9, 4),
+                                        # a second pass of the Bellman-target loop; both limits; a third pass with one row
+                                        (5, 3, 65, 33), (2, 256, 256, 64), (4, 1, 129, 64)])
 def test_head_kernel_has_the_bits_of_the_four_launches_it_replaces(B, NP, NPP, A, kappa):
     g = torch.Generator().manual_seed(100 * B + NP)
     zc, zt = torch.randn(B, NP, A, generator=g), torch.randn(B, NPP, A, generator=g)
@@ -128,7 +130,9 @@ def _mix_reference(feat, taus, We, be):
 
 
 @pytest.mark.parametrize("nprob", [1, 3])
-@pytest.mark.parametrize("B,n,Ed,H", [(33, 5, 16, 48), (8, 1, 10, 30), (2, 9, 8, 4), (64, 8, 64, 512)])
+@pytest.mark.parametrize("B,n,Ed,H", [(33, 5, 16, 48), (8, 1, 10, 30), (2, 9, 8, 4), (64, 8, 64, 512),
+                                      # full LDS panels with a one-column block; E % 8 = 7; E = 17 on unaligned rows
+                                      (3, 2, 128, 65), (2, 3, 127, 64), (5, 7, 17, 30)])
 def test_mix_kernel_has_the_bits_of_cos_embed_gemm_hadamard(B, n, Ed, H, nprob):
     g = torch.Generator().manual_seed(B + H + nprob)
     probs, keep, want = (N.IqnMixProb * nprob)(), [], []
