@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define PORL_ABI_VERSION 11
+#define PORL_ABI_VERSION 12
 #define PORL_MAX_HIDDEN 8
 
 #define PORL_OK 0
@@ -140,6 +140,13 @@ int porl_iql_set_mode(porl_iql* h, int32_t mode);
 /* Redirect where the next updates write their 3 loss statistics (>= 8 floats, 16-byte aligned): lets a
  * training loop keep a device-side loss history without copies or host syncs. */
 int porl_iql_set_stats(porl_iql* h, float* stats);
+
+/* How the last Adam launch of `group` (0 = value, 1 = policy) dealt with the combine jobs handed to it (read-only; all
+ * zero before the group's first launch, and for a launch without pending jobs):
+ *   out[0] jobs summed inside the float4 sweep (regions),  out[1] / out[2] jobs folded as reduce+Adam blocks at width
+ *   32 / width 4,  out[3] jobs outside the gradient buffer (loss statistics: plain reduce blocks),  out[4] ranges the
+ *   sweep skips,  out[5] reduce blocks in front of the sweep blocks. */
+int porl_iql_adam_plan(const porl_iql* h, int group, int32_t out[6]);
 
 typedef struct porl_iql_hyper {
   float tau;         /* expectile                                   */

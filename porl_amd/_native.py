@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libporl_hip.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 # every symbol include/porl_hip.h declares (tests check the .so exports exactly these)
 SYMBOLS = [
@@ -19,6 +19,7 @@ SYMBOLS = [
     "porl_iql_create", "porl_iql_destroy", "porl_iql_group_floats", "porl_iql_group_tensors",
     "porl_iql_tensor_info", "porl_iql_workspace_floats", "porl_iql_bind", "porl_iql_load_batch",
     "porl_iql_load_batch_sampled", "porl_iql_load_batch_indexed", "porl_iql_set_stats", "porl_iql_set_mode", "porl_iql_tune_set",
+    "porl_iql_adam_plan",
     "porl_iql_value_backward", "porl_iql_value_apply", "porl_iql_policy_forward", "porl_iql_policy_backward",
     "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_only_forward", "porl_iql_policy_only_step", "porl_iql_policy_prefetch", "porl_iql_forward_value", "porl_iql_forward_policy",
     "porl_gemm_f32", "porl_gemm_f32_group", "porl_adam_ema", "porl_ema", "porl_softmax_mask", "porl_gather_rows", "porl_sample_indices", "porl_epoch_indices", "porl_per_update", "porl_per_sample",
@@ -177,6 +178,7 @@ def _declare(lib):
     lib.porl_iql_load_batch_indexed.argtypes = [vp, i32, vp, i64, i64, vp, i32, i32, i32, i32, vp, i64, vp, i64, vp]
     lib.porl_iql_set_stats.argtypes = [vp, vp]
     lib.porl_iql_set_mode.argtypes = [vp, i32]
+    lib.porl_iql_adam_plan.argtypes = [vp, C.c_int, C.POINTER(i32 * 6)]
     for name in ("porl_iql_value_backward", "porl_iql_value_apply", "porl_iql_policy_forward", "porl_iql_policy_backward",
                  "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_only_forward", "porl_iql_policy_only_step"):
         getattr(lib, name).argtypes = [vp, C.POINTER(IqlHyper), vp]

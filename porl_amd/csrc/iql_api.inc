@@ -76,6 +76,7 @@ struct porl_iql {
   int slot = 0;                     // batch slot of the most recent load
   ReduceArgs fin_v{}, fin_p{};      // PORL_IQL_MODE_FOLD_COMBINE: combines left pending by *_backward for *_apply
   bool fin_v_pending = false, fin_p_pending = false;
+  int32_t adam_plan[2][6] = {};     // porl_iql_adam_plan: what the last Adam launch of each group did with its jobs
   int batch = 0;
   bool have_pol_target = false;
   bool pol_prefetched = false;      // porl_iql_policy_prefetch ran for the loaded batch: policy forward is done
@@ -497,7 +498,8 @@ int value_backward_impl(porl_iql* h, const porl_iql_hyper* hp, hipStream_t s, Re
 int value_adam(porl_iql* h, const porl_iql_hyper* hp, hipStream_t s, const ReduceArgs* fin) {
   g_phase = "V8.";
   const int rc = adam_launch(h->buf.params_vf, h->buf.grads_vf, h->buf.adam_m_vf, h->buf.adam_v_vf, h->buf.params_tgt, h->n_vf,
-                             hp->value_lr, hp->value_step, hp->adam_beta1, hp->adam_beta2, hp->adam_eps, hp->ema_beta, s, fin);
+                             hp->value_lr, hp->value_step, hp->adam_beta1, hp->adam_beta2, hp->adam_eps, hp->ema_beta, s, fin,
+                             h->adam_plan[0]);
   g_phase = "";
   return rc;
 }
@@ -507,7 +509,7 @@ int value_adam(porl_iql* h, const porl_iql_hyper* hp, hipStream_t s, const Reduc
 int policy_adam(porl_iql* h, const porl_iql_hyper* hp, hipStream_t s, const ReduceArgs* fin, const char* phase) {
   g_phase = phase;
   const int rc = adam_launch(h->buf.params_pol, h->buf.grads_pol, h->buf.adam_m_pol, h->buf.adam_v_pol, nullptr, h->n_pol,
-                             hp->policy_lr, hp->policy_step, hp->adam_beta1, hp->adam_beta2, hp->adam_eps, 0.0, s, fin);
+                             hp->policy_lr, hp->policy_step, hp->adam_beta1, hp->adam_beta2, hp->adam_eps, 0.0, s, fin, h->adam_plan[1]);
   g_phase = "";
   return rc;
 }
@@ -871,6 +873,13 @@ int porl_iql_set_stats(porl_iql* h, float* stats) {
   PORL_TRY(check_ready(h, false));
   if (!stats) PORL_FAIL(PORL_ERR_INVALID, "null stats");
   h->buf.stats = stats;
+  return PORL_OK;
+}
+
+int porl_iql_adam_plan(const porl_iql* h, int group, int32_t out[6]) {
+  if (!h || !out) PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  if (group < 0 || group > 1) PORL_FAIL(PORL_ERR_INVALID, "bad group");
+  std::copy(h->adam_plan[group], h->adam_plan[group] + 6, out);
   return PORL_OK;
 }
 

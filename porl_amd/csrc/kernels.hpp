@@ -403,13 +403,17 @@ struct AdamArgs {
 };
 
 // Polyak update of one element (util/util.py:54-56): target <- (1 - beta) * target + beta * source.  One definition
-// for the fused sweep and the stand-alone kernel, so both round the same way.
-__device__ __forceinline__ float ema1(float t, float p, float omeb, float ema_beta) { return t * omeb + ema_beta * p; }
+// for the fused sweep, the reduce+Adam blocks and the stand-alone kernel, and one EXPLICIT rounding: t * omeb is rounded,
+// ema_beta * p is fused into the sum.  Written as `t * omeb + ema_beta * p` the compiler chose per call site — that fma
+// in the float4 sweep, two rounded products and an add in the scalar reduce+Adam branch — so a target element stepped by
+// a reduce block differed in the last bit from the same element stepped by the sweep (tests/test_adam_fold_gpu.py).
+__device__ __forceinline__ float ema1(float t, float p, float omeb, float ema_beta) { return __fmaf_rn(ema_beta, p, t * omeb); }
 
+// The same for Adam: the forms below are the ones both branches compiled to; stated, so that they stay one form.
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamScalars& s) {
-  m = m + s.omb1 * (g - m);
-  v = v * s.beta2 + s.omb2 * g * g;
-  p = p - s.step_size * (m / (sqrtf(v) / s.bc2_sqrt + s.eps));
+  m = __fmaf_rn(s.omb1, g - m, m);
+  v = __fmaf_rn(s.omb2 * g, g, v * s.beta2);
+  p = __fmaf_rn(-s.step_size, m / (sqrtf(v) / s.bc2_sqrt + s.eps), p);
 }
 
 __global__ __launch_bounds__(256) void adam_ema_kernel(const AdamArgs a) {

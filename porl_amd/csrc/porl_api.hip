@@ -356,7 +356,8 @@ int feistel_half_bits(int64_t n_rows) {
 // output lies inside the gradient buffer `g` are folded into this launch (short slab lists inside the float4 sweep,
 // long ones as extra reduce+Adam blocks), the others (loss statistics) ride along as plain reduce blocks.
 int adam_launch(float* p, float* g, float* m, float* v, float* tgt, int64_t n, double lr, int step,
-                       double b1, double b2, double eps, double ema_beta, hipStream_t s, const ReduceArgs* fin = nullptr) {
+                       double b1, double b2, double eps, double ema_beta, hipStream_t s, const ReduceArgs* fin = nullptr,
+                       int32_t* plan = nullptr) {
   if (n < 0 || n % 4) PORL_FAIL(PORL_ERR_INVALID, "adam range must be a non-negative multiple of 4 floats");
   if (step < 1) PORL_FAIL(PORL_ERR_INVALID, "adam step must be >= 1");
   if (n == 0 && !(fin && fin->njobs)) return PORL_OK;      // an empty range is an empty sweep (the grid maths below divide by it)
@@ -376,6 +377,7 @@ int adam_launch(float* p, float* g, float* m, float* v, float* tgt, int64_t n, d
   a.span4 = sweep_blocks ? ((a.n4 + sweep_blocks - 1) / sweep_blocks + 255) / 256 * 256 : 256;
   int reduce_blocks = 0;
   double extra_bytes = 0.0;
+  int32_t nplan[6] = {0, 0, 0, 0, 0, 0};      // porl_iql_adam_plan: regions, folded width 32 / 4, unfolded, skips, blocks
   if (fin) {
     for (int q = 0; q < fin->njobs; ++q) {
       ReduceJob j = fin->job[q];
@@ -387,14 +389,17 @@ int adam_launch(float* p, float* g, float* m, float* v, float* tgt, int64_t n, d
           aligned16(j.slab) && a.nregions < MAX_ADAM_REGIONS) {
         AdamRegion& R = a.region[a.nregions++];
         R.lo = off; R.hi = off + j.n; R.slab = j.slab; R.stride = j.stride; R.nslab = j.nslab;
+        ++nplan[0];
         continue;
       }
       if (inside) {
         if (off % 4) PORL_FAIL(PORL_ERR_INVALID, "gradient tensors start on 16-byte boundaries");
         j.adam_off = off;
         a.skip_lo[a.nskip] = off; a.skip_hi[a.nskip] = ru4(off + j.n); ++a.nskip;
+        ++nplan[j.width == 4 ? 2 : 1];
       } else {
         j.adam_off = -1;
+        ++nplan[3];
       }
       a.job_block0[a.r.njobs] = reduce_blocks;
       a.r.job[a.r.njobs++] = j;
@@ -404,6 +409,10 @@ int adam_launch(float* p, float* g, float* m, float* v, float* tgt, int64_t n, d
   }
   ProfScope ps("adam_ema_kernel", s, 0.0, (double)n * (tgt ? 36.0 : 28.0) + extra_bytes);
   a.reduce_blocks = reduce_blocks;
+  if (plan) {
+    nplan[4] = a.nskip; nplan[5] = reduce_blocks;
+    std::copy(nplan, nplan + 6, plan);
+  }
   hipLaunchKernelGGL(adam_ema_kernel, dim3(sweep_blocks + reduce_blocks), dim3(256), 0, s, a);
   PORL_HIP(hipGetLastError());
   return PORL_OK;

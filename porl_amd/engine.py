@@ -128,6 +128,16 @@ class IqlEngine:
         """porl_tune_set for this engine only (it copied the process defaults when it was created)."""
         N.check(self._lib.porl_iql_tune_set(self._h, key.encode(), int(value)), "porl_iql_tune_set")
 
+    ADAM_PLAN = ("regions", "fold32", "fold4", "unfolded", "skips", "reduce_blocks")
+
+    def adam_plan(self, group):
+        """How the last Adam launch of `group` dealt with the combine jobs handed to it (porl_iql_adam_plan): jobs summed
+        inside the sweep, folded as reduce+Adam blocks at width 32 / 4, left as plain reduce blocks (loss statistics),
+        ranges the sweep skips, reduce blocks.  Read-only; synchronises nothing."""
+        out = (C.c_int32 * 6)()
+        N.check(self._lib.porl_iql_adam_plan(self._h, int(group), C.byref(out)), "porl_iql_adam_plan")
+        return dict(zip(self.ADAM_PLAN, out))
+
     # -- memory ------------------------------------------------------------------------------------
     # Flat groups are allocated a little longer than the C library needs (zero tail) so that they split into equal,
     # 16-byte-aligned slices for every data-parallel world size that divides 840 (1..8, 10, 12, ...): the

@@ -166,6 +166,19 @@ int main() {
     REJECT_UNTOUCHED(porl_iql_load_batch_sampled(h, 32, x, 124, 1000, 2, 1, 1, 0, nullptr, nullptr), "policy target width");
 #undef REJECT_UNTOUCHED
   }
+  {
+    // porl_iql_adam_plan: a host-side read of what the last Adam launch of a group did; all zero before the first one
+    int32_t plan[6] = {7, 7, 7, 7, 7, 7};
+    REJECT(porl_iql_adam_plan(nullptr, 0, plan));
+    REJECT(porl_iql_adam_plan(h, 0, nullptr));
+    REJECT_MSG(porl_iql_adam_plan(h, -1, plan), "bad group");
+    REJECT_MSG(porl_iql_adam_plan(h, 2, plan), "bad group");
+    if (plan[0] != 7 || plan[5] != 7) { ++g_bad; std::fprintf(stderr, "a rejected porl_iql_adam_plan wrote its output\n"); }
+    for (int g = 0; g < 2; ++g) {
+      ACCEPT(porl_iql_adam_plan(h, g, plan));
+      for (int k = 0; k < 6; ++k) if (plan[k] != 0) { ++g_bad; std::fprintf(stderr, "adam plan of group %d not zero before a launch\n", g); }
+    }
+  }
   REJECT(porl_iql_tune_set(h, "no_such_key", 1));
   REJECT(porl_iql_tune_set(h, nullptr, 1));
   ACCEPT(porl_iql_tune_set(h, "skinny", 0));

@@ -53,7 +53,7 @@ def test_abi_declares_the_entry_point():
     txt = open(os.path.join(REPO, "include", "porl_hip.h")).read()
     assert re.search(r"\bint\s+porl_astar_label\s*\(", txt)
     assert "porl_astar_label" in N.SYMBOLS
-    assert N.ABI_VERSION == 11 and N.lib().porl_abi_version() == 11
+    assert N.ABI_VERSION == 12 and N.lib().porl_abi_version() == 12
     for k, name in enumerate(("LABELLED", "TOO_CLOSE", "GOAL_IS_START", "GOAL_OFF_GRID", "GOAL_BLOCKED", "UNREACHABLE",
                               "NON_FINITE", "NOT_CONVERGED")):
         assert re.search(rf"PORL_ASTAR_{name}\s*=\s*{k}\b", txt), name

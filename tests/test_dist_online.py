@@ -64,4 +64,4 @@ def test_trainers_name_the_learn_on_their_one_call_step_reproduces():
             def learn_on(self, *batch):
                 return 0.0
         assert Mine._rows_for is not Mine.learn_on         # overriding learn_on opts out of the one-call step
-    assert C.sizeof(N.DistHead) == 32 and N.ABI_VERSION == 11
+    assert C.sizeof(N.DistHead) == 32 and N.ABI_VERSION == 12

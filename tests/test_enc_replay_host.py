@@ -37,7 +37,7 @@ def test_ctypes_table_matches_the_header():
         for p, t in zip(params, fn.argtypes):
             want = N.C.c_void_p if "*" in p else {"int32_t": N.C.c_int32, "int64_t": N.C.c_int64}[p.split()[0]]
             assert t is want, (name, p, t)
-    assert lib.porl_abi_version() == N.ABI_VERSION == 11
+    assert lib.porl_abi_version() == N.ABI_VERSION == 12
 
 
 def test_signatures():

@@ -99,8 +99,8 @@ def test_abi_declares_the_entry_points():
         assert re.search(rf"\b(int|int64_t)\s+{name}\s*\(", txt), name
         assert name in N.SYMBOLS
         assert hasattr(N.lib(), name)
-    assert re.search(r"#define\s+PORL_ABI_VERSION\s+11\b", txt)
-    assert N.ABI_VERSION == 11 and N.lib().porl_abi_version() == 11
+    assert re.search(r"#define\s+PORL_ABI_VERSION\s+12\b", txt)
+    assert N.ABI_VERSION == 12 and N.lib().porl_abi_version() == 12
 
 
 def test_tile_constants_are_exported():

@@ -105,7 +105,7 @@ def test_abi_declares_the_entry_points():
         assert hasattr(N.lib(), name)
     assert re.search(r"typedef struct porl_partition_box\s*\{\s*int32_t cx, cy;[^}]*float x_lo, x_hi, y_lo, y_hi;\s*\}", txt)
     assert C.sizeof(N.PartitionBox) == 24
-    assert re.search(r"#define\s+PORL_ABI_VERSION\s+11\b", txt)                    # additions only
+    assert re.search(r"#define\s+PORL_ABI_VERSION\s+12\b", txt)                    # additions only
 
 
 def test_tile_constants_are_exported():

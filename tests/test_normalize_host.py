@@ -154,8 +154,8 @@ def test_abi_declares_the_entry_points():
         assert hasattr(N.lib(), name)
     assert re.search(r"typedef struct porl_col_span\s*\{\s*int32_t col0, n_cols, param0, flags;\s*\}\s*porl_col_span;", txt)
     assert C.sizeof(N.ColSpan) == 16
-    assert re.search(r"#define\s+PORL_ABI_VERSION\s+11\b", txt)                    # additions only
-    assert N.ABI_VERSION == 11 and N.lib().porl_abi_version() == 11
+    assert re.search(r"#define\s+PORL_ABI_VERSION\s+12\b", txt)                    # additions only
+    assert N.ABI_VERSION == 12 and N.lib().porl_abi_version() == 12
 
 
 def test_workspace_sizes():
