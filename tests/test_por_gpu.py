@@ -763,11 +763,14 @@ def test_adam_sweep_over_an_empty_range_is_a_no_op():
                                           (64, 192, 1, 2100, False), (8, 72, 2, 64, True), (60, 512, 3, 2048, False)])
 def test_skinny_kernels_agree_with_the_grouped_gemm_path(S, H, L, B, sorl):
     """The <= 64-wide products of the step (input-layer weight gradients, policy mean, policy output-layer backward) run
-    on csrc/skinny.hpp; porl_tune_set("skinny", 0) sends them through the grouped GEMM as in round 2.  Same partial sums
-    per 64-chunk in another order, so from IDENTICAL state (three updates; both paths' backward passes run on every
-    update before the parameters move) gradients and losses agree to fp32 rounding.  Covers ragged shapes, more than 16
-    row tiles (several tiles per slab) and SORL's 2-wide output layer; both paths are pinned to the reference by the
-    golden tests above.  (Whole trajectories are NOT compared: Adam's first steps turn a 1e-10 gradient difference on
+    on csrc/skinny.hpp.  The `skinny` tune key is a bit mask, one bit per product: 1 = wgrad_skinny_kernel (dW0), 2 =
+    mean_skinny_kernel (policy mean), 4 = out_bwd_kernel (policy output layer); 0 sends all three through the grouped
+    GEMM as in round 2, 7 is the default, and porl_tune_set reads the value 1 as "all" (7), so no value selects
+    wgrad_skinny_kernel alone.  Mask 0 is compared with the mean kernel alone (2), out_bwd_kernel alone (4), both without
+    the dW0 kernel (6), and all three (7, and 1 which must mean the same).  Same partial sums per 64-chunk in another
+    order, so from IDENTICAL state (three updates; every mask's backward passes run on every update before the
+    parameters move) gradients and losses agree to fp32 rounding.  Covers ragged shapes, more than 16 row tiles (several
+    tiles per slab) and SORL's 2-wide output layer; both paths are pinned to the reference by the golden tests above.  (Whole trajectories are NOT compared: Adam's first steps turn a 1e-10 gradient difference on
     a |g| ~ 1e-8 entry into a 1e-6 parameter difference, and ReLU-mask flips do the rest.)"""
     from porl_amd.agent.sorl import SORL
     from porl_amd.engine import IqlEngine
@@ -789,14 +792,15 @@ def test_skinny_kernels_agree_with_the_grouped_gemm_path(S, H, L, B, sorl):
         hp = agent._hyper(Bk, v_opt, p_opt)
         for phase, group, apply in (("value_backward", 0, "value_apply"), ("policy_backward", 1, "policy_apply")):
             got = {}
-            for skinny in (0, 1):
+            for skinny in (0, 1, 2, 4, 6, 7):       # the default, 7, is the one left set for the apply
                 eng.tune_set("skinny", skinny)
                 getattr(eng, phase)(hp)
                 flat = eng.grads_vf if group == 0 else eng.grads_pol
                 got[skinny] = ([g.clone() for g in IqlEngine.views(flat, eng.tensor_table(group))], eng.stats[:3].clone())
-            for i, (g0, g1) in enumerate(zip(got[0][0], got[1][0])):
-                scale = float(g0.abs().max())
-                assert float((g0 - g1).abs().max()) <= 1e-6 * scale + 1e-12, (k, phase, i, scale)
-            np.testing.assert_allclose(got[1][1].cpu().numpy(), got[0][1].cpu().numpy(), rtol=1e-6)
+            for skinny in (1, 2, 4, 6, 7):
+                for i, (g0, g1) in enumerate(zip(got[0][0], got[skinny][0])):
+                    scale = float(g0.abs().max())
+                    assert float((g0 - g1).abs().max()) <= 1e-6 * scale + 1e-12, (k, phase, skinny, i, scale)
+                np.testing.assert_allclose(got[skinny][1].cpu().numpy(), got[0][1].cpu().numpy(), rtol=1e-6)
             getattr(eng, apply)(hp)
         sched.step()
