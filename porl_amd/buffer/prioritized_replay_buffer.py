@@ -141,8 +141,7 @@ class PrioritizedReplayBuffer:
             self._alloc(state)
         st = self._store
         sdim = st["states"].shape[1]
-        from ..train.cql_trainer import QnetEngine
-        if sdim > QnetEngine.RECORD_MAX_STATE:                 # PORL_RECORD_MAX_STATE: the row rides in the kernel's arguments
+        if sdim > E.QnetEngine.RECORD_MAX_STATE:                 # PORL_RECORD_MAX_STATE: the row rides in the kernel's arguments
             self.add(td_error, *experience)
             return False
         if self._pending:

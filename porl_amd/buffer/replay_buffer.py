@@ -56,15 +56,14 @@ class ReplayBuffer:
         mirror when there is none.  Returns True when the mirror row was written now; False when the state is too wide
         for the kernel's arguments and the row took `push`'s deferred path.  Without `engine` a minimal engine of the
         buffer's state width is made once."""
-        from ..train.cql_trainer import QnetEngine
         p = self.position
         S = self._flat_states(self.states).shape[1]
-        if S > QnetEngine.RECORD_MAX_STATE:
+        if S > E.QnetEngine.RECORD_MAX_STATE:
             self.push(state, action, reward, next_state, done)
             return False
         if engine is None:
             if getattr(self, "_rec_engine", None) is None:    # a minimal engine of this state width: the handle the call needs
-                self._rec_engine = QnetEngine(S, 1, [1], 1, self.device)
+                self._rec_engine = E.QnetEngine(S, 1, [1], 1, self.device)
                 self._rec_engine._ensure_bound()
             engine = self._rec_engine
         self.states[p] = state

@@ -1,4 +1,6 @@
-"""Host-side owner of one IQL-family update engine (POR / SORL) on one MI355X.
+"""The ctypes layer over libporl_hip.so's three engines on one MI355X: IqlEngine (POR / SORL), QnetEngine (the
+Q-learning trainers' MLPs) and IqnEngine.  Every native call on an engine handle is a method of its class here;
+`replay_args` is the one check of device-resident replay arrays in front of the row-sourced steps.
 
 PyTorch supplies device memory and the stream; all arithmetic of the step runs in libporl_hip.so
 (porl_amd/_native.py).  Parameters, gradients and Adam moments each live in ONE flat fp32 tensor per
@@ -409,6 +411,322 @@ class IqlEngine:
             pass
 
 
+def replay_args(states, actions, rewards, next_states, dones, state_dim, device, n_rows=None, idx=None):
+    """The one check of device-resident replay arrays in front of a row-sourced native call: each array contiguous, of its
+    dtype, on `device` and (with `n_rows`) at least that long, rows `state_dim` wide, `idx` (if given) contiguous int64 on
+    `device`.  Raises RuntimeError naming the offending array; returns the arrays as the C ABI takes them:
+    (states, s_rs, actions, rewards, next_states, n_rs, dones)."""
+    short = n_rows is not None
+    for name, x, dt in (("states", states, torch.float32), ("next_states", next_states, torch.float32),
+                        ("actions", actions, torch.int64), ("rewards", rewards, torch.float32),
+                        ("dones", dones, torch.float32)):
+        if x.dtype != dt or x.device != device or not x.is_contiguous() or (short and x.shape[0] < n_rows):
+            rows = "" if n_rows is None else f" of >= {n_rows} rows"
+            raise RuntimeError(f"{name}: need a contiguous {dt} tensor{rows} on {device}")
+    if states.shape[1:].numel() != state_dim:
+        raise RuntimeError(f"states: rows of {states.shape[1:].numel()} floats, the network's state_dim is {state_dim}")
+    if next_states.shape != states.shape:
+        raise RuntimeError(f"next_states: shape {tuple(next_states.shape)}, states have {tuple(states.shape)}")
+    if idx is not None and (idx.dtype != torch.int64 or idx.device != device or not idx.is_contiguous()):
+        raise RuntimeError(f"idx: need a contiguous torch.int64 tensor on {device}")
+    return N.ptr(states), state_dim, N.ptr(actions), N.ptr(rewards), N.ptr(next_states), state_dim, N.ptr(dones)
+
+
+class QnetEngine:
+    """The Q-network engine of the C ABI (porl_qnet_*): every ctypes call on its handle is a method here."""
+
+    def __init__(self, state_dim, n_actions, hidden, max_batch, device):
+        self.device = _norm_device(device)
+        hid = (C.c_int32 * 8)(*hidden)
+        self.cfg = N.QnetCfg(int(state_dim), int(n_actions), len(hidden), hid, int(max_batch))
+        self._lib = N.lib()
+        h = C.c_void_p()
+        N.check(self._lib.porl_qnet_create(C.byref(self.cfg), C.byref(h)), "porl_qnet_create")
+        self._h = h
+        self.n_params = int(self._lib.porl_qnet_param_floats(h))
+        z = lambda: torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
+        self.params, self.params_tgt, self.grads, self.adam_m, self.adam_v = z(), z(), z(), z(), z()
+        self.stats = torch.zeros(8, dtype=torch.float32, device=self.device)
+        self.workspace, self._bound = None, False
+
+    @property
+    def fused(self):
+        """True when the network fits the one-launch step kernel (csrc/qnet_fused.hpp)."""
+        return bool(self._lib.porl_qnet_one_launch(self._h))
+
+    def tensor_table(self):
+        """[(offset, shape, row stride)] — weight matrices sit inside zero-padded images (include/porl_hip.h)."""
+        out = []
+        off, r, c, ld = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
+        for i in range(int(self._lib.porl_qnet_tensors(self._h))):
+            N.check(self._lib.porl_qnet_tensor_info(self._h, i, C.byref(off), C.byref(r), C.byref(c), C.byref(ld)))
+            out.append((off.value, (c.value,) if r.value == 0 else (r.value, c.value), ld.value))
+        return out
+
+    def views(self, flat):
+        """Parameter-shaped views into a flat group (weights: strided (out, in) windows of their padded images)."""
+        return [flat[o:o + s[0]] if len(s) == 1 else flat[o:o + s[0] * ld].view(s[0], ld)[:, :s[1]]
+                for o, s, ld in self.tensor_table()]
+
+    def adopt(self, mod, which=0, params=None):
+        """Move a module onto this engine: copy its parameters (`params`: the ones the engine owns, default all) into the
+        views of the online (0) / target (1) group, re-point them there, and route the module's forward to the engine."""
+        with torch.no_grad():
+            for p, v in zip(mod.parameters() if params is None else params,
+                            self.views(self.params if which == 0 else self.params_tgt)):
+                v.copy_(p)
+                p.data = v
+        mod._engine, mod._which = self, which
+
+    def _ensure_bound(self):
+        if self.device.type != "cuda":
+            raise N.NativeError("porl_amd computes on a HIP device only (device='cuda'); there is no CPU path")
+        if self._bound:
+            return
+        self.workspace = torch.empty(int(self._lib.porl_qnet_workspace_floats(self._h)), dtype=torch.float32,
+                                     device=self.device)
+        b = N.QnetBuffers(*[C.c_void_p(t.data_ptr()) for t in (self.params, self.params_tgt, self.grads,
+                                                                 self.adam_m, self.adam_v, self.workspace, self.stats)])
+        N.check(self._lib.porl_qnet_bind(self._h, C.byref(b)), "porl_qnet_bind")
+        self._bound = True
+
+    def _states(self, x, what="states"):
+        if x.dtype != torch.float32:
+            x = x.float()
+        x = x.reshape(x.shape[0], -1)
+        if x.shape[1] != self.cfg.state_dim:
+            raise RuntimeError(f"{what}: expected (B, {self.cfg.state_dim}), got {tuple(x.shape)}")
+        if x.device != self.device:
+            raise RuntimeError(f"{what} on {x.device}, engine on {self.device}")
+        return x if x.stride(1) == 1 else x.contiguous()
+
+    def load_batch(self, states, actions, rewards, next_states, dones):
+        self._ensure_bound()
+        states, next_states = self._states(states), self._states(next_states, "next_states")
+        B = states.shape[0]
+        if B > self.cfg.max_batch:
+            raise RuntimeError(f"batch {B} exceeds engine max_batch {self.cfg.max_batch}")
+        if actions.dtype != torch.int64:
+            actions = actions.long()
+        rewards, dones = rewards.float(), dones.float()
+        self._held = (states, actions, rewards, next_states, dones)
+        N.check(self._lib.porl_qnet_load_batch(self._h, B, N.ptr(states), states.stride(0), N.ptr(actions),
+                                               actions.stride(0), N.ptr(rewards), rewards.stride(0),
+                                               N.ptr(next_states), next_states.stride(0), N.ptr(dones),
+                                               dones.stride(0), N.current_stream_ptr(self.device)), "porl_qnet_load_batch")
+        return B
+
+    def hyper(self, gamma, alpha, inv_batch, step, lr, betas=(0.9, 0.999), eps=1e-8):
+        return N.QnetHyper(gamma, alpha, inv_batch, step, lr, betas[0], betas[1], eps)
+
+    post_step = None      # callable(hp) run after every optimizer step of this engine (dueling heads: _DuelingHeads)
+
+    def _stepped(self, hp):
+        if self.post_step is not None:
+            self.post_step(hp)
+
+    def cql_backward(self, hp): N.check(self._lib.porl_qnet_cql_backward(self._h, C.byref(hp), N.current_stream_ptr(self.device)), "porl_qnet_cql_backward")
+
+    def apply(self, hp):
+        N.check(self._lib.porl_qnet_apply(self._h, C.byref(hp), N.current_stream_ptr(self.device)), "porl_qnet_apply")
+        self._stepped(hp)
+
+    def learn(self, hp):
+        N.check(self._lib.porl_qnet_learn(self._h, C.byref(hp), N.current_stream_ptr(self.device)), "porl_qnet_learn")
+        self._stepped(hp)
+
+    # -- the loaded minibatch, stage by stage (the distributional trainers' learn_on) ---------------------------------
+    def forward_loaded(self, which_params, which_input, keep, out):
+        """Forward of the online (0) / target (1) parameters on the loaded states (0) / next states (1) into `out`;
+        `keep`: hold the activations for backward()."""
+        self._ensure_bound()
+        N.check(self._lib.porl_qnet_forward_loaded(self._h, which_params, which_input, int(keep), N.ptr(out), out.stride(0),
+                                                   N.current_stream_ptr(self.device)), "porl_qnet_forward_loaded")
+        return out
+
+    def backward(self, dout):
+        """Backward of the kept forward from dL/d(output) `dout` into the gradient group."""
+        self._ensure_bound()
+        N.check(self._lib.porl_qnet_backward(self._h, N.ptr(dout), dout.stride(0), N.current_stream_ptr(self.device)),
+                "porl_qnet_backward")
+
+    # -- row-sourced steps: the replay arrays stay where they are, the kernels read rows of them -----------------------
+    def _replay(self, batch, states, actions, rewards, next_states, dones, n_rows=None, idx=None):
+        """What every row-sourced step does first: bound engine, batch within max_batch, replay_args."""
+        self._ensure_bound()
+        cfg = self.cfg
+        if batch > cfg.max_batch:
+            raise RuntimeError(f"batch {batch} exceeds engine max_batch {cfg.max_batch}")
+        return replay_args(states, actions, rewards, next_states, dones, cfg.state_dim, self.device, n_rows, idx)
+
+    def learn_indexed(self, hp, states, actions, rewards, next_states, dones, idx, variant=None):
+        """learn() on rows `idx` (int64, device) of device-resident replay arrays: gathered inside the one-launch step
+        kernel, or — networks with a layer wider than 128 or more than five Linear layers — by one gather launch in
+        front of the multi-launch path (same loss arithmetic, incl. the Double-DQN / importance-weight / BCQ-mask
+        variants)."""
+        B = idx.numel()
+        args = self._replay(B, states, actions, rewards, next_states, dones, idx=idx)
+        if variant is None:
+            N.check(self._lib.porl_qnet_learn_indexed(self._h, *args, N.ptr(idx), B, C.byref(hp),
+                                                      N.current_stream_ptr(self.device)), "porl_qnet_learn_indexed")
+        else:
+            N.check(self._lib.porl_qnet_learn_variant(self._h, *args, N.ptr(idx), B, C.byref(hp), C.byref(variant),
+                                                      N.current_stream_ptr(self.device)), "porl_qnet_learn_variant")
+        self._stepped(hp)
+        return B
+
+    def learn_sampled(self, hp, states, actions, rewards, next_states, dones, n_rows, batch, seed, draw, variant=None):
+        """learn() on `batch` distinct rows of the first `n_rows` rows of device-resident replay arrays, drawn inside
+        the step kernel (the indices of engine.sample_indices(n_rows, batch, seed, draw), never materialised); `variant`:
+        a QnetVariant, e.g. td_off for BCQ's pre-training."""
+        args = self._replay(batch, states, actions, rewards, next_states, dones, n_rows)
+        draw_ = (int(n_rows), int(seed), int(draw), int(batch), C.byref(hp))
+        if variant is None:
+            N.check(self._lib.porl_qnet_learn_sampled(self._h, *args, *draw_, N.current_stream_ptr(self.device)),
+                    "porl_qnet_learn_sampled")
+        else:
+            N.check(self._lib.porl_qnet_learn_sampled_variant(self._h, *args, *draw_, C.byref(variant),
+                                                              N.current_stream_ptr(self.device)),
+                    "porl_qnet_learn_sampled_variant")
+        self._stepped(hp)
+        return batch
+
+    def dist_learn(self, hp, states, actions, rewards, next_states, dones, idx, head):
+        """One C51 / QR-DQN step (N.DistHead `head`) on rows `idx` from one native call (porl_qnet_dist_learn): gather,
+        the forwards grouped per layer, loss head, backward, Adam; the mean loss lands in stats[0]."""
+        B = idx.numel()
+        args = self._replay(B, states, actions, rewards, next_states, dones, idx=idx)
+        if B < 1:
+            raise RuntimeError(f"batch {B} outside [1, {self.cfg.max_batch}]")
+        N.check(self._lib.porl_qnet_dist_learn(self._h, *args, N.ptr(idx), B, C.byref(hp), C.byref(head),
+                                               N.current_stream_ptr(self.device)), "porl_qnet_dist_learn")
+        return B
+
+    # -- discrete BCQ (csrc/bcq_mask.hpp): `self` holds the behaviour policy in bcq_mask, the Q-networks in bcq_learn_* ----
+    def bcq_mask(self, next_states, idx, threshold, out=None):
+        """(B, A) fp32 0/1 mask of the actions whose behaviour probability in next_states[idx[b]] exceeds `threshold`
+        (porl_qnet_bcq_mask; this engine's online parameters are the behaviour policy)."""
+        self._ensure_bound()
+        B, A = idx.numel(), self.cfg.n_actions
+        if next_states.dtype != torch.float32 or next_states.device != self.device or not next_states.is_contiguous() or \
+                next_states.shape[1:].numel() != self.cfg.state_dim:
+            raise RuntimeError(f"next_states: need contiguous float32 rows of {self.cfg.state_dim} on {self.device}")
+        if idx.dtype != torch.int64 or idx.device != self.device or not idx.is_contiguous():
+            raise RuntimeError(f"idx: need a contiguous torch.int64 tensor on {self.device}")
+        if out is None:
+            out = torch.empty(B, A, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() or out.numel() < B * A:
+            raise RuntimeError(f"out: need >= {B * A} contiguous float32 on {self.device}")
+        N.check(self._lib.porl_qnet_bcq_mask(self._h, N.ptr(next_states), self.cfg.state_dim, N.ptr(idx), B, float(threshold),
+                                             N.ptr(out), N.current_stream_ptr(self.device)), "porl_qnet_bcq_mask")
+        return out
+
+    def bcq_learn_indexed(self, beh_engine, hp, states, actions, rewards, next_states, dones, idx, threshold):
+        """One BCQ step on rows `idx` of the replay arrays from one native call (porl_qnet_bcq_learn): behaviour mask of
+        `beh_engine`, masked-argmax step, Adam."""
+        B = idx.numel()
+        args = self._replay(B, states, actions, rewards, next_states, dones, idx=idx)
+        beh_engine._ensure_bound()
+        N.check(self._lib.porl_qnet_bcq_learn(self._h, beh_engine._h, *args, N.ptr(idx), B, C.byref(hp), float(threshold),
+                                              N.current_stream_ptr(self.device)), "porl_qnet_bcq_learn")
+        self._stepped(hp)
+        return B
+
+    def bcq_learn_sampled(self, beh_engine, hp, states, actions, rewards, next_states, dones, n_rows, batch, seed, draw,
+                          threshold):
+        """bcq_learn_indexed on the rows engine.sample_indices(n_rows, batch, seed, draw) would give, drawn inside the
+        mask kernel and the step kernel (porl_qnet_bcq_learn_sampled); needs can_sample."""
+        args = self._replay(batch, states, actions, rewards, next_states, dones, n_rows)
+        beh_engine._ensure_bound()
+        N.check(self._lib.porl_qnet_bcq_learn_sampled(
+            self._h, beh_engine._h, *args, int(n_rows), int(seed), int(draw), int(batch), C.byref(hp), float(threshold),
+            N.current_stream_ptr(self.device)), "porl_qnet_bcq_learn_sampled")
+        self._stepped(hp)
+        return batch
+
+    @property
+    def can_sample(self):
+        return bool(self._lib.porl_qnet_can_sample(self._h))
+
+    post_sync = None      # callable() run after the target network was overwritten (dueling heads)
+
+    def sync_target(self):
+        self._ensure_bound()
+        N.check(self._lib.porl_qnet_sync_target(self._h, N.current_stream_ptr(self.device)), "porl_qnet_sync_target")
+        if self.post_sync is not None:
+            self.post_sync()
+
+    def forward(self, x, which=0):
+        self._ensure_bound()
+        x = self._states(x)
+        q = torch.empty(x.shape[0], self.cfg.n_actions, dtype=torch.float32, device=self.device)
+        N.check(self._lib.porl_qnet_forward(self._h, which, N.ptr(x), x.stride(0), x.shape[0], N.ptr(q),
+                                            self.cfg.n_actions, N.current_stream_ptr(self.device)), "porl_qnet_forward")
+        return q
+
+    # -- online loop (csrc/online.hpp) ----------------------------------------------------------------
+    RECORD_MAX_STATE = 480          # PORL_RECORD_MAX_STATE: 2 x state_dim floats ride in the record kernel's arguments
+    ACT_MAX_BATCH = 8
+    ACT_MAX_INLINE = 256            # floats of inline states per act launch
+
+    def record(self, mirror, slot, state, next_state, action, reward, done):
+        """Write one transition (host float32 rows `state` / `next_state`) into row `slot` of a device replay mirror
+        (the dict of ReplayBuffer._mirror) with one launch; the values travel in the kernel's arguments."""
+        self._ensure_bound()
+        key = tuple(mirror[k].data_ptr() for k in ("states", "next_states", "actions", "rewards", "dones"))
+        if getattr(self, "_mirror_key", None) != key:
+            replay_args(mirror["states"], mirror["actions"], mirror["rewards"], mirror["next_states"], mirror["dones"],
+                        self.cfg.state_dim, self.device)
+            self._mirror_c = N.QnetMirror(*[C.c_void_p(p) for p in key], int(mirror["states"].shape[0]))
+            self._mirror_key = key
+        N.check(self._lib.porl_qnet_record(self._h, int(slot), state.ctypes.data, next_state.ctypes.data, int(action),
+                                           float(reward), float(done), C.byref(self._mirror_c),
+                                           N.current_stream_ptr(self.device)), "porl_qnet_record")
+
+    @property
+    def act_ok(self):
+        """True when the network suits the one-workgroup act kernel (every layer <= 1024 wide, <= 2^19 parameter floats)."""
+        return bool(self._lib.porl_qnet_act_ok(self._h))
+
+    def act(self, out, states=None, row=0, batch=1, inline=None, which=0, kind=0, n_act=0, n_sub=1, support=None,
+            stats=None, n_stats=0):
+        """Greedy action(s) in one launch (porl_qnet_act) into the int32 record `out` (16 words, device or pinned host):
+        out[:batch] = argmax_a Q(s_b, a) of rows [row, row + batch) of the device array `states`, or of `inline`
+        (host float32, batch x state_dim); out[8:8+n_stats] (as fp32) = stats[:n_stats] (None: the engine's statistics).
+        kind 0: argmax of the outputs; 1: C51 expectation over n_sub atoms with `support`; 2: QR mean of n_sub quantiles."""
+        self._ensure_bound()
+        if states is not None:
+            if states.dtype != torch.float32 or states.device != self.device or states.stride(-1) != 1:
+                raise RuntimeError(f"states: need float32 rows on {self.device}")
+            src = N.QnetActSrc(int(batch), states.data_ptr(), states.stride(0), int(row), states.shape[0], None)
+        else:
+            inline = np.ascontiguousarray(inline, dtype=np.float32)
+            src = N.QnetActSrc(int(batch), None, self.cfg.state_dim, 0, 0, inline.ctypes.data)
+        epi = N.QnetActEpilogue(int(kind), int(n_act), int(n_sub), None if support is None else support.data_ptr(),
+                                None if stats is None else stats.data_ptr(), int(n_stats))
+        N.check(self._lib.porl_qnet_act(self._h, int(which), C.byref(src), C.byref(epi), C.c_void_p(out.data_ptr()),
+                                        N.current_stream_ptr(self.device)), "porl_qnet_act")
+        return out
+
+    def penalty(self, states, actions):
+        self._ensure_bound()
+        states = self._states(states)
+        actions = actions.long()
+        out = torch.empty(1, dtype=torch.float32, device=self.device)
+        N.check(self._lib.porl_qnet_penalty(self._h, N.ptr(states), states.stride(0), N.ptr(actions),
+                                            actions.stride(0), states.shape[0], N.ptr(out),
+                                            N.current_stream_ptr(self.device)), "porl_qnet_penalty")
+        return out[0]
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.porl_qnet_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
 class IqnEngine:
     """The IQN engine of the C ABI (porl_iqn_*): one learn step / one greedy action of IQNTrainer per native call, on flat
     buffers the caller owns (`bind`).  Tensors in IQNNetwork.parameters() order, each starting on a 16-byte boundary —
@@ -454,19 +772,13 @@ class IqnEngine:
         """One learn step on rows `idx` (int64, device) of the replay arrays (porl_iqn_learn); the mean loss, the total
         gradient norm and the clip coefficient land in stats[0:3]."""
         B = idx.numel()
-        for name, x, dt in (("states", states, torch.float32), ("next_states", next_states, torch.float32),
-                            ("actions", actions, torch.int64), ("rewards", rewards, torch.float32),
-                            ("dones", dones, torch.float32), ("idx", idx, torch.int64),
-                            ("taus_prime", taus_prime, torch.float32), ("taus_double_prime", taus_double_prime, torch.float32)):
-            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
-                raise RuntimeError(f"{name}: need a contiguous {dt} tensor on {self.device}")
-        S = self.cfg.state_dim
-        if states.shape[1:].numel() != S or next_states.shape != states.shape:
-            raise RuntimeError("replay arrays do not match the network's state_dim")
-        if taus_prime.dim() != 2 or taus_double_prime.dim() != 2 or taus_prime.shape[0] != B or taus_double_prime.shape[0] != B:
-            raise RuntimeError("fractions: expected (batch, n) tensors")
-        N.check(self._lib.porl_iqn_learn(self._h, N.ptr(states), S, N.ptr(actions), N.ptr(rewards), N.ptr(next_states), S,
-                                         N.ptr(dones), N.ptr(idx), B, N.ptr(taus_prime), taus_prime.shape[1],
+        args = replay_args(states, actions, rewards, next_states, dones, self.cfg.state_dim, self.device, idx=idx)
+        for name, x in (("taus_prime", taus_prime), ("taus_double_prime", taus_double_prime)):
+            if x.dtype != torch.float32 or x.device != self.device or not x.is_contiguous():
+                raise RuntimeError(f"{name}: need a contiguous {torch.float32} tensor on {self.device}")
+            if x.dim() != 2 or x.shape[0] != B:
+                raise RuntimeError(f"{name}: fractions come as a (batch, n) tensor, got {tuple(x.shape)} for batch {B}")
+        N.check(self._lib.porl_iqn_learn(self._h, *args, N.ptr(idx), B, N.ptr(taus_prime), taus_prime.shape[1],
                                          N.ptr(taus_double_prime), taus_double_prime.shape[1], C.byref(hp),
                                          N.current_stream_ptr(self.device)), "porl_iqn_learn")
         return B

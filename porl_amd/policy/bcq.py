@@ -24,6 +24,8 @@ import math
 import torch
 
 from .. import _native as N
+from .. import engine as E
+from ..train.cql_trainer import learn_minibatch, read_losses
 
 
 def collect_dataset(env, agent, num_episodes: int = 1000) -> None:
@@ -40,16 +42,7 @@ def collect_dataset(env, agent, num_episodes: int = 1000) -> None:
 
 
 def _step(agent, eng, opt, batch, alpha, variant):
-    states, actions, rewards, next_states, dones = batch
-    states, next_states = eng._states(states).contiguous(), eng._states(next_states, "next_states").contiguous()
-    B = states.shape[0]
-    opt.step_count += 1
-    g = opt.param_groups[0]
-    hp = eng.hyper(agent.gamma, alpha, 1.0 / B, opt.step_count, g["lr"], g["betas"], g["eps"])
-    idx = torch.arange(B, dtype=torch.int64, device=eng.device)
-    eng.learn_indexed(hp, states, actions.long().contiguous(), rewards.float().contiguous(), next_states,
-                      dones.float().contiguous(), idx, variant=variant)
-    return eng.stats
+    return learn_minibatch(eng, opt, agent.gamma, alpha, batch, variant)
 
 
 def bcq_behavior_pretrain(agent):
@@ -69,20 +62,11 @@ def bcq_learn(agent) -> float:
     batch = agent.replay_buffer.sample(agent.batch_size)
     mask = agent.behavior_policy.sample(batch[3], agent.threshold)      # (B, A) over next_states
     var = N.QnetVariant(0, None, None, None, mask.data_ptr(), 0)
-    stats = _step(agent, agent._engine, agent.optimizer, batch, 0.0, var)
-    if agent.async_losses:
-        return stats[:3]
-    loss, agent.last_td_loss, _ = stats[:3].tolist()
-    return loss
+    _step(agent, agent._engine, agent.optimizer, batch, 0.0, var)
+    return read_losses(agent)
 
 
 # -- device-rows forms ----------------------------------------------------------------------------------------------------
-def _hyper(agent, eng, opt, alpha, B):
-    opt.step_count += 1
-    g = opt.param_groups[0]
-    return eng.hyper(agent.gamma, alpha, 1.0 / B, opt.step_count, g["lr"], g["betas"], g["eps"])
-
-
 def _learn_gathered(agent, idx):
     """Today's pieces on the gathered rows (data-parallel exchange active: the step must not be fused into one call)."""
     batch = agent.replay_buffer.gather_device(idx)
@@ -91,21 +75,15 @@ def _learn_gathered(agent, idx):
     return _step(agent, agent._engine, agent.optimizer, batch, 0.0, var)
 
 
-def _loss_out(agent, stats):
-    if agent.async_losses:
-        return stats[:3]
-    loss, agent.last_td_loss, _ = stats[:3].tolist()
-    return loss
-
-
 def _launch_rows(agent, idx):
     rb = agent.replay_buffer
     if agent._exchange.active:
         return _learn_gathered(agent, idx)
     eng, m = agent._engine, rb._mirror
-    hp = _hyper(agent, eng, agent.optimizer, 0.0, idx.numel())
+    hp = agent.optimizer.hyper(agent.gamma, 0.0, 1.0 / idx.numel())
     eng.bcq_learn_indexed(agent._behavior_engine, hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"],
                           idx, agent.threshold)
+    agent.optimizer.step_count = hp.step
     return eng.stats
 
 
@@ -113,7 +91,8 @@ def bcq_learn_rows(agent, idx):
     """bcq_learn on rows `idx` (device int64) of the replay mirror -> loss (float, or the device statistics view with
     agent.async_losses)."""
     agent.replay_buffer._sync_mirror()
-    return _loss_out(agent, _launch_rows(agent, idx))
+    _launch_rows(agent, idx)
+    return read_losses(agent)
 
 
 def _next_draw(agent, batch):
@@ -128,24 +107,23 @@ def _next_draw(agent, batch):
 
 def bcq_learn_device_sampled(agent, seed=0):
     """bcq_learn with the B distinct rows drawn on the device (draw counter shared with learn_device_sampled)."""
-    from .. import engine as E
     rb, eng, B = agent.replay_buffer, agent._engine, agent.batch_size
     draw = _next_draw(agent, B)
     if agent._exchange.active or not eng.can_sample:
-        idx = E.sample_indices(rb.size, B, seed, draw, device=agent.device)
-        return _loss_out(agent, _launch_rows(agent, idx))
+        _launch_rows(agent, E.sample_indices(rb.size, B, seed, draw, device=agent.device))
+        return read_losses(agent)
     m = rb._mirror
-    hp = _hyper(agent, eng, agent.optimizer, 0.0, B)
+    hp = agent.optimizer.hyper(agent.gamma, 0.0, 1.0 / B)
     eng.bcq_learn_sampled(agent._behavior_engine, hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"],
                           rb.size, B, seed, draw, agent.threshold)
-    return _loss_out(agent, eng.stats)
+    agent.optimizer.step_count = hp.step
+    return read_losses(agent)
 
 
 def bcq_pretrain_device_sampled(agent, seed=0):
     """bcq_behavior_pretrain on device-drawn rows -> list of the per-epoch cross-entropy losses.  Each epoch's statistic
     is copied device to device into a (num_epochs,) log that is read back once at the end."""
-    from .. import engine as E
-    rb, eng, B = agent.replay_buffer, agent._behavior_engine, agent.batch_size
+    rb, eng, opt, B = agent.replay_buffer, agent._behavior_engine, agent.behavior_optimizer, agent.batch_size
     ln_a = math.log(agent.action_size)
     var = N.QnetVariant(0, None, None, None, None, 1)                  # td_off: loss = penalty = CE - ln A
     log = torch.zeros(max(agent.num_epochs, 1), dtype=torch.float32, device=eng.device)
@@ -153,15 +131,16 @@ def bcq_pretrain_device_sampled(agent, seed=0):
         draw = _next_draw(agent, B)
         if agent._exchange.active:
             idx = E.sample_indices(rb.size, B, seed, draw, device=agent.device)
-            _step(agent, eng, agent.behavior_optimizer, rb.gather_device(idx), 1.0, var)
+            _step(agent, eng, opt, rb.gather_device(idx), 1.0, var)
         else:
             m = rb._mirror
-            hp = _hyper(agent, eng, agent.behavior_optimizer, 1.0, B)
+            hp = opt.hyper(agent.gamma, 1.0, 1.0 / B)
             args = (m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"])
             if eng.can_sample:
-                eng.learn_sampled_variant(hp, *args, rb.size, B, seed, draw, var)
+                eng.learn_sampled(hp, *args, rb.size, B, seed, draw, variant=var)
             else:
                 idx = E.sample_indices(rb.size, B, seed, draw, device=agent.device)
                 eng.learn_indexed(hp, *args, idx, variant=var)
+            opt.step_count = hp.step
         log[epoch:epoch + 1].copy_(eng.stats[2:3])
     return [v + ln_a for v in log[:agent.num_epochs].tolist()]

@@ -8,7 +8,8 @@ import torch
 
 from ..net.behavior_policy import BehaviorPolicy
 from ..net.q_network import QNetwork
-from .cql_trainer import QnetEngine, _FlatAdam
+from ..engine import QnetEngine
+from .cql_trainer import _FlatAdam
 from .dqn_trainer import DQNTrainer
 
 
@@ -23,11 +24,7 @@ class BCQTrainer(DQNTrainer):
         self.behavior_policy = behavior_policy(state_size, action_size)
         hidden = self.behavior_policy._spec[2]
         eng = QnetEngine(state_size, action_size, hidden, self._engine.cfg.max_batch, self.device)
-        with torch.no_grad():
-            for p, v in zip(self.behavior_policy.parameters(), eng.views(eng.params)):
-                v.copy_(p)
-                p.data = v
-        self.behavior_policy._engine = eng
+        eng.adopt(self.behavior_policy)
         self._behavior_engine = eng
         self.behavior_optimizer = _FlatAdam(eng, list(self.behavior_policy.parameters()), 0.0005)
 

@@ -31,13 +31,13 @@ class C51Trainer(DistTrainerBase):
 
     def learn_on(self, states, actions, rewards, next_states, dones):
         B, actions, rewards, dones = self._load((states, actions, rewards, next_states, dones))
-        lc = self._forward_loaded(0, 0, True, self._out[0][:B])
-        lt = self._forward_loaded(1, 1, False, self._out[2][:B])
+        lc = self._engine.forward_loaded(0, 0, True, self._out[0][:B])
+        lt = self._engine.forward_loaded(1, 1, False, self._out[2][:B])
         dl = self._dout[:B]
-        N.check(self._engine._lib.porl_c51_loss(N.ptr(lc), N.ptr(lt), lc.stride(0), N.ptr(actions), N.ptr(rewards),
-                                                N.ptr(dones), N.ptr(self.support), B, self.action_size, self.atom_size,
-                                                self.gamma, float(self.v_min), float(self.v_max), N.ptr(dl),
-                                                N.ptr(self._row_loss), N.current_stream_ptr(self.device)), "porl_c51_loss")
+        N.check(N.lib().porl_c51_loss(N.ptr(lc), N.ptr(lt), lc.stride(0), N.ptr(actions), N.ptr(rewards),
+                                      N.ptr(dones), N.ptr(self.support), B, self.action_size, self.atom_size,
+                                      self.gamma, float(self.v_min), float(self.v_max), N.ptr(dl),
+                                      N.ptr(self._row_loss), N.current_stream_ptr(self.device)), "porl_c51_loss")
         return self._backward_and_step(dl, B)
 
     _rows_for = learn_on

@@ -9,324 +9,26 @@ intended (`learning_rate` defaults to the hard-coded 5e-4 of dqn_trainer.py:71).
 
 `learn()` = sample (host index stream identical to the reference under the same numpy seed, gather on the
 device) + one fused device update: target forward, online forward, TD + CQL(H) penalty, backward, Adam —
-hand-written gfx950 kernels behind `porl_qnet_*` (include/porl_hip.h).
+hand-written gfx950 kernels behind `porl_qnet_*` (include/porl_hip.h), reached through engine.QnetEngine (the ctypes
+layer, with the one replay-array check `engine.replay_args`).
+
+Host bookkeeping every Q-learning trainer shares lives here: `_FlatAdam.hyper` builds the hyper-parameters of the NEXT
+Adam step without advancing anything — a caller makes its native call(s) and then sets `step_count = hp.step`, so a
+refused call leaves the optimizer where it was; `read_losses` is the one read-back of the step statistics, `checked_loss`
+the reference's IndexError for an action outside 0..A-1, `learn_minibatch` the step on an explicit minibatch.
 """
 from __future__ import annotations
 
-import ctypes as C
-import math
-
 import numpy as np
 import torch
-import torch.nn as nn
 
-from .. import _native as N
+from .. import engine as E
 from ..buffer.replay_buffer import ReplayBuffer
-from ..engine import _norm_device
+from ..engine import QnetEngine                                     # (tests and scripts import it from here)
 from ..net.q_network import DuelingQNetwork, QNetwork
 from ..parallel import GradExchange
 from ..utils.logger import Logger
-
-
-class QnetEngine:
-    def __init__(self, state_dim, n_actions, hidden, max_batch, device):
-        self.device = _norm_device(device)
-        hid = (C.c_int32 * 8)(*hidden)
-        self.cfg = N.QnetCfg(int(state_dim), int(n_actions), len(hidden), hid, int(max_batch))
-        self._lib = N.lib()
-        h = C.c_void_p()
-        N.check(self._lib.porl_qnet_create(C.byref(self.cfg), C.byref(h)), "porl_qnet_create")
-        self._h = h
-        self.n_params = int(self._lib.porl_qnet_param_floats(h))
-        z = lambda: torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
-        self.params, self.params_tgt, self.grads, self.adam_m, self.adam_v = z(), z(), z(), z(), z()
-        self.stats = torch.zeros(8, dtype=torch.float32, device=self.device)
-        self.workspace, self._bound = None, False
-
-    @property
-    def fused(self):
-        """True when the network fits the one-launch step kernel (csrc/qnet_fused.hpp)."""
-        return bool(self._lib.porl_qnet_one_launch(self._h))
-
-    def tensor_table(self):
-        """[(offset, shape, row stride)] — weight matrices sit inside zero-padded images (include/porl_hip.h)."""
-        out = []
-        off, r, c, ld = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
-        for i in range(int(self._lib.porl_qnet_tensors(self._h))):
-            N.check(self._lib.porl_qnet_tensor_info(self._h, i, C.byref(off), C.byref(r), C.byref(c), C.byref(ld)))
-            out.append((off.value, (c.value,) if r.value == 0 else (r.value, c.value), ld.value))
-        return out
-
-    def views(self, flat):
-        """Parameter-shaped views into a flat group (weights: strided (out, in) windows of their padded images)."""
-        return [flat[o:o + s[0]] if len(s) == 1 else flat[o:o + s[0] * ld].view(s[0], ld)[:, :s[1]]
-                for o, s, ld in self.tensor_table()]
-
-    def _ensure_bound(self):
-        if self.device.type != "cuda":
-            raise N.NativeError("porl_amd computes on a HIP device only (device='cuda'); there is no CPU path")
-        if self._bound:
-            return
-        self.workspace = torch.empty(int(self._lib.porl_qnet_workspace_floats(self._h)), dtype=torch.float32,
-                                     device=self.device)
-        b = N.QnetBuffers(*[C.c_void_p(t.data_ptr()) for t in (self.params, self.params_tgt, self.grads,
-                                                                 self.adam_m, self.adam_v, self.workspace, self.stats)])
-        N.check(self._lib.porl_qnet_bind(self._h, C.byref(b)), "porl_qnet_bind")
-        self._bound = True
-
-    def _states(self, x, what="states"):
-        if x.dtype != torch.float32:
-            x = x.float()
-        x = x.reshape(x.shape[0], -1)
-        if x.shape[1] != self.cfg.state_dim:
-            raise RuntimeError(f"{what}: expected (B, {self.cfg.state_dim}), got {tuple(x.shape)}")
-        if x.device != self.device:
-            raise RuntimeError(f"{what} on {x.device}, engine on {self.device}")
-        return x if x.stride(1) == 1 else x.contiguous()
-
-    def load_batch(self, states, actions, rewards, next_states, dones):
-        self._ensure_bound()
-        states, next_states = self._states(states), self._states(next_states, "next_states")
-        B = states.shape[0]
-        if B > self.cfg.max_batch:
-            raise RuntimeError(f"batch {B} exceeds engine max_batch {self.cfg.max_batch}")
-        if actions.dtype != torch.int64:
-            actions = actions.long()
-        rewards, dones = rewards.float(), dones.float()
-        self._held = (states, actions, rewards, next_states, dones)
-        N.check(self._lib.porl_qnet_load_batch(self._h, B, N.ptr(states), states.stride(0), N.ptr(actions),
-                                               actions.stride(0), N.ptr(rewards), rewards.stride(0),
-                                               N.ptr(next_states), next_states.stride(0), N.ptr(dones),
-                                               dones.stride(0), N.current_stream_ptr(self.device)), "porl_qnet_load_batch")
-        return B
-
-    def hyper(self, gamma, alpha, inv_batch, step, lr, betas=(0.9, 0.999), eps=1e-8):
-        return N.QnetHyper(gamma, alpha, inv_batch, step, lr, betas[0], betas[1], eps)
-
-    post_step = None      # callable(hp) run after every optimizer step of this engine (dueling heads: _DuelingHeads)
-
-    def _stepped(self, hp):
-        if self.post_step is not None:
-            self.post_step(hp)
-
-    def cql_backward(self, hp): N.check(self._lib.porl_qnet_cql_backward(self._h, C.byref(hp), N.current_stream_ptr(self.device)), "porl_qnet_cql_backward")
-
-    def apply(self, hp):
-        N.check(self._lib.porl_qnet_apply(self._h, C.byref(hp), N.current_stream_ptr(self.device)), "porl_qnet_apply")
-        self._stepped(hp)
-
-    def learn(self, hp):
-        N.check(self._lib.porl_qnet_learn(self._h, C.byref(hp), N.current_stream_ptr(self.device)), "porl_qnet_learn")
-        self._stepped(hp)
-
-    def learn_indexed(self, hp, states, actions, rewards, next_states, dones, idx, variant=None):
-        """learn() on rows `idx` (int64, device) of device-resident replay arrays: gathered inside the one-launch step
-        kernel, or — networks with a layer wider than 128 or more than five Linear layers — by one gather launch in
-        front of the multi-launch path (same loss arithmetic, incl. the Double-DQN / importance-weight / BCQ-mask
-        variants)."""
-        self._ensure_bound()
-        B = idx.numel()
-        if B > self.cfg.max_batch:
-            raise RuntimeError(f"batch {B} exceeds engine max_batch {self.cfg.max_batch}")
-        for name, x, dt in (("states", states, torch.float32), ("next_states", next_states, torch.float32),
-                            ("actions", actions, torch.int64), ("rewards", rewards, torch.float32),
-                            ("dones", dones, torch.float32), ("idx", idx, torch.int64)):
-            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
-                raise RuntimeError(f"{name}: need a contiguous {dt} tensor on {self.device}")
-        if states.shape[1:].numel() != self.cfg.state_dim or next_states.shape != states.shape:
-            raise RuntimeError("replay arrays do not match the network's state_dim")
-        if variant is None:
-            N.check(self._lib.porl_qnet_learn_indexed(self._h, N.ptr(states), self.cfg.state_dim, N.ptr(actions),
-                                                      N.ptr(rewards), N.ptr(next_states), self.cfg.state_dim, N.ptr(dones),
-                                                      N.ptr(idx), B, C.byref(hp), N.current_stream_ptr(self.device)),
-                    "porl_qnet_learn_indexed")
-        else:
-            N.check(self._lib.porl_qnet_learn_variant(self._h, N.ptr(states), self.cfg.state_dim, N.ptr(actions),
-                                                      N.ptr(rewards), N.ptr(next_states), self.cfg.state_dim, N.ptr(dones),
-                                                      N.ptr(idx), B, C.byref(hp), C.byref(variant),
-                                                      N.current_stream_ptr(self.device)), "porl_qnet_learn_variant")
-        self._stepped(hp)
-        return B
-
-    def learn_sampled(self, hp, states, actions, rewards, next_states, dones, n_rows, batch, seed, draw):
-        """learn() on `batch` distinct rows of the first `n_rows` rows of device-resident replay arrays, drawn inside
-        the step kernel (the indices of engine.sample_indices(n_rows, batch, seed, draw), never materialised)."""
-        self._ensure_bound()
-        if batch > self.cfg.max_batch:
-            raise RuntimeError(f"batch {batch} exceeds engine max_batch {self.cfg.max_batch}")
-        for name, x, dt in (("states", states, torch.float32), ("next_states", next_states, torch.float32),
-                            ("actions", actions, torch.int64), ("rewards", rewards, torch.float32),
-                            ("dones", dones, torch.float32)):
-            if x.dtype != dt or x.device != self.device or not x.is_contiguous() or x.shape[0] < n_rows:
-                raise RuntimeError(f"{name}: need a contiguous {dt} tensor of >= {n_rows} rows on {self.device}")
-        if states.shape[1:].numel() != self.cfg.state_dim or next_states.shape != states.shape:
-            raise RuntimeError("replay arrays do not match the network's state_dim")
-        N.check(self._lib.porl_qnet_learn_sampled(self._h, N.ptr(states), self.cfg.state_dim, N.ptr(actions), N.ptr(rewards),
-                                                  N.ptr(next_states), self.cfg.state_dim, N.ptr(dones), int(n_rows),
-                                                  int(seed), int(draw), int(batch), C.byref(hp),
-                                                  N.current_stream_ptr(self.device)), "porl_qnet_learn_sampled")
-        self._stepped(hp)
-        return batch
-
-    def _check_replay(self, states, actions, rewards, next_states, dones, n_rows, batch, idx=None):
-        """The checks learn_indexed / learn_sampled make inline (those two are left as they were on purpose: every other
-        trainer calls them), shared by the entry points below."""
-        if batch > self.cfg.max_batch:
-            raise RuntimeError(f"batch {batch} exceeds engine max_batch {self.cfg.max_batch}")
-        for name, x, dt in (("states", states, torch.float32), ("next_states", next_states, torch.float32),
-                            ("actions", actions, torch.int64), ("rewards", rewards, torch.float32),
-                            ("dones", dones, torch.float32)):
-            if x.dtype != dt or x.device != self.device or not x.is_contiguous() or x.shape[0] < n_rows:
-                raise RuntimeError(f"{name}: need a contiguous {dt} tensor of >= {n_rows} rows on {self.device}")
-        if states.shape[1:].numel() != self.cfg.state_dim or next_states.shape != states.shape:
-            raise RuntimeError("replay arrays do not match the network's state_dim")
-        if idx is not None and (idx.dtype != torch.int64 or idx.device != self.device or not idx.is_contiguous()):
-            raise RuntimeError(f"idx: need a contiguous torch.int64 tensor on {self.device}")
-
-    def learn_sampled_variant(self, hp, states, actions, rewards, next_states, dones, n_rows, batch, seed, draw, variant):
-        """learn_sampled with a QnetVariant (porl_qnet_learn_sampled_variant), e.g. td_off for BCQ's pre-training."""
-        self._ensure_bound()
-        self._check_replay(states, actions, rewards, next_states, dones, n_rows, batch)
-        N.check(self._lib.porl_qnet_learn_sampled_variant(
-            self._h, N.ptr(states), self.cfg.state_dim, N.ptr(actions), N.ptr(rewards), N.ptr(next_states),
-            self.cfg.state_dim, N.ptr(dones), int(n_rows), int(seed), int(draw), int(batch), C.byref(hp), C.byref(variant),
-            N.current_stream_ptr(self.device)), "porl_qnet_learn_sampled_variant")
-        self._stepped(hp)
-        return batch
-
-    # -- discrete BCQ (csrc/bcq_mask.hpp): `self` holds the behaviour policy in bcq_mask, the Q-networks in bcq_learn_* ----
-    def bcq_mask(self, next_states, idx, threshold, out=None):
-        """(B, A) fp32 0/1 mask of the actions whose behaviour probability in next_states[idx[b]] exceeds `threshold`
-        (porl_qnet_bcq_mask; this engine's online parameters are the behaviour policy)."""
-        self._ensure_bound()
-        B, A = idx.numel(), self.cfg.n_actions
-        if next_states.dtype != torch.float32 or next_states.device != self.device or not next_states.is_contiguous() or \
-                next_states.shape[1:].numel() != self.cfg.state_dim:
-            raise RuntimeError(f"next_states: need contiguous float32 rows of {self.cfg.state_dim} on {self.device}")
-        if idx.dtype != torch.int64 or idx.device != self.device or not idx.is_contiguous():
-            raise RuntimeError(f"idx: need a contiguous torch.int64 tensor on {self.device}")
-        if out is None:
-            out = torch.empty(B, A, dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous() or out.numel() < B * A:
-            raise RuntimeError(f"out: need >= {B * A} contiguous float32 on {self.device}")
-        N.check(self._lib.porl_qnet_bcq_mask(self._h, N.ptr(next_states), self.cfg.state_dim, N.ptr(idx), B, float(threshold),
-                                             N.ptr(out), N.current_stream_ptr(self.device)), "porl_qnet_bcq_mask")
-        return out
-
-    def bcq_learn_indexed(self, beh_engine, hp, states, actions, rewards, next_states, dones, idx, threshold):
-        """One BCQ step on rows `idx` of the replay arrays from one native call (porl_qnet_bcq_learn): behaviour mask of
-        `beh_engine`, masked-argmax step, Adam."""
-        self._ensure_bound()
-        beh_engine._ensure_bound()
-        B = idx.numel()
-        self._check_replay(states, actions, rewards, next_states, dones, 0, B, idx)
-        N.check(self._lib.porl_qnet_bcq_learn(
-            self._h, beh_engine._h, N.ptr(states), self.cfg.state_dim, N.ptr(actions), N.ptr(rewards), N.ptr(next_states),
-            self.cfg.state_dim, N.ptr(dones), N.ptr(idx), B, C.byref(hp), float(threshold),
-            N.current_stream_ptr(self.device)), "porl_qnet_bcq_learn")
-        self._stepped(hp)
-        return B
-
-    def bcq_learn_sampled(self, beh_engine, hp, states, actions, rewards, next_states, dones, n_rows, batch, seed, draw,
-                          threshold):
-        """bcq_learn_indexed on the rows engine.sample_indices(n_rows, batch, seed, draw) would give, drawn inside the
-        mask kernel and the step kernel (porl_qnet_bcq_learn_sampled); needs can_sample."""
-        self._ensure_bound()
-        beh_engine._ensure_bound()
-        self._check_replay(states, actions, rewards, next_states, dones, n_rows, batch)
-        N.check(self._lib.porl_qnet_bcq_learn_sampled(
-            self._h, beh_engine._h, N.ptr(states), self.cfg.state_dim, N.ptr(actions), N.ptr(rewards), N.ptr(next_states),
-            self.cfg.state_dim, N.ptr(dones), int(n_rows), int(seed), int(draw), int(batch), C.byref(hp), float(threshold),
-            N.current_stream_ptr(self.device)), "porl_qnet_bcq_learn_sampled")
-        self._stepped(hp)
-        return batch
-
-    @property
-    def can_sample(self):
-        return bool(self._lib.porl_qnet_can_sample(self._h))
-
-    post_sync = None      # callable() run after the target network was overwritten (dueling heads)
-
-    def sync_target(self):
-        self._ensure_bound()
-        N.check(self._lib.porl_qnet_sync_target(self._h, N.current_stream_ptr(self.device)), "porl_qnet_sync_target")
-        if self.post_sync is not None:
-            self.post_sync()
-
-    def forward(self, x, which=0):
-        self._ensure_bound()
-        x = self._states(x)
-        q = torch.empty(x.shape[0], self.cfg.n_actions, dtype=torch.float32, device=self.device)
-        N.check(self._lib.porl_qnet_forward(self._h, which, N.ptr(x), x.stride(0), x.shape[0], N.ptr(q),
-                                            self.cfg.n_actions, N.current_stream_ptr(self.device)), "porl_qnet_forward")
-        return q
-
-    # -- online loop (csrc/online.hpp) ----------------------------------------------------------------
-    RECORD_MAX_STATE = 480          # PORL_RECORD_MAX_STATE: 2 x state_dim floats ride in the record kernel's arguments
-    ACT_MAX_BATCH = 8
-    ACT_MAX_INLINE = 256            # floats of inline states per act launch
-
-    def record(self, mirror, slot, state, next_state, action, reward, done):
-        """Write one transition (host float32 rows `state` / `next_state`) into row `slot` of a device replay mirror
-        (the dict of ReplayBuffer._mirror) with one launch; the values travel in the kernel's arguments."""
-        self._ensure_bound()
-        key = tuple(mirror[k].data_ptr() for k in ("states", "next_states", "actions", "rewards", "dones"))
-        if getattr(self, "_mirror_key", None) != key:
-            for k, dt in (("states", torch.float32), ("next_states", torch.float32), ("actions", torch.int64),
-                          ("rewards", torch.float32), ("dones", torch.float32)):
-                t = mirror[k]
-                if t.dtype != dt or t.device != self.device or not t.is_contiguous():
-                    raise RuntimeError(f"mirror {k}: need a contiguous {dt} tensor on {self.device}")
-            if mirror["states"].shape[1:].numel() != self.cfg.state_dim or mirror["next_states"].shape != mirror["states"].shape:
-                raise RuntimeError("mirror rows do not match the engine's state_dim")
-            self._mirror_c = N.QnetMirror(*[C.c_void_p(p) for p in key], int(mirror["states"].shape[0]))
-            self._mirror_key = key
-        N.check(self._lib.porl_qnet_record(self._h, int(slot), state.ctypes.data, next_state.ctypes.data, int(action),
-                                           float(reward), float(done), C.byref(self._mirror_c),
-                                           N.current_stream_ptr(self.device)), "porl_qnet_record")
-
-    @property
-    def act_ok(self):
-        """True when the network suits the one-workgroup act kernel (every layer <= 1024 wide, <= 2^19 parameter floats)."""
-        return bool(self._lib.porl_qnet_act_ok(self._h))
-
-    def act(self, out, states=None, row=0, batch=1, inline=None, which=0, kind=0, n_act=0, n_sub=1, support=None,
-            stats=None, n_stats=0):
-        """Greedy action(s) in one launch (porl_qnet_act) into the int32 record `out` (16 words, device or pinned host):
-        out[:batch] = argmax_a Q(s_b, a) of rows [row, row + batch) of the device array `states`, or of `inline`
-        (host float32, batch x state_dim); out[8:8+n_stats] (as fp32) = stats[:n_stats] (None: the engine's statistics).
-        kind 0: argmax of the outputs; 1: C51 expectation over n_sub atoms with `support`; 2: QR mean of n_sub quantiles."""
-        self._ensure_bound()
-        if states is not None:
-            if states.dtype != torch.float32 or states.device != self.device or states.stride(-1) != 1:
-                raise RuntimeError(f"states: need float32 rows on {self.device}")
-            src = N.QnetActSrc(int(batch), states.data_ptr(), states.stride(0), int(row), states.shape[0], None)
-        else:
-            inline = np.ascontiguousarray(inline, dtype=np.float32)
-            src = N.QnetActSrc(int(batch), None, self.cfg.state_dim, 0, 0, inline.ctypes.data)
-        epi = N.QnetActEpilogue(int(kind), int(n_act), int(n_sub), None if support is None else support.data_ptr(),
-                                None if stats is None else stats.data_ptr(), int(n_stats))
-        N.check(self._lib.porl_qnet_act(self._h, int(which), C.byref(src), C.byref(epi), C.c_void_p(out.data_ptr()),
-                                        N.current_stream_ptr(self.device)), "porl_qnet_act")
-        return out
-
-    def penalty(self, states, actions):
-        self._ensure_bound()
-        states = self._states(states)
-        actions = actions.long()
-        out = torch.empty(1, dtype=torch.float32, device=self.device)
-        N.check(self._lib.porl_qnet_penalty(self._h, N.ptr(states), states.stride(0), N.ptr(actions),
-                                            actions.stride(0), states.shape[0], N.ptr(out),
-                                            N.current_stream_ptr(self.device)), "porl_qnet_penalty")
-        return out[0]
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.porl_qnet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+from . import online
 
 
 class _DuelingHeads:
@@ -371,7 +73,6 @@ class _DuelingHeads:
 
     def compose(self, which):
         """Write the composed output layer of the online (0) / target (1) network into the engine's parameter image."""
-        from .. import engine as E
         A, F, eng = self.A, self.F, self.eng
         hd = self._hd(self.flat if which == 0 else self.flat_tgt)
         E.gemm_f32(1, self.M, hd, A, F + 1, A + 1, A + 1, F + 1, self.w_ext, F + 1)          # (A, A+1) x (A+1, F+1)
@@ -381,7 +82,6 @@ class _DuelingHeads:
             views[-1].copy_(self.w_ext[:, F])
 
     def after_step(self, hp):
-        from .. import engine as E
         A, F, eng = self.A, self.F, self.eng
         gv = eng.views(eng.grads)
         with torch.no_grad():
@@ -409,7 +109,13 @@ class _FlatAdam:
     def zero_grad(self, set_to_none=True):
         pass
 
-    _dueling = None       # _DuelingHeads of a DuelingQNetwork trainer: the heads' moments live beside the engine's
+    def hyper(self, gamma, alpha, inv_batch):
+        """QnetHyper of the next Adam step (step_count + 1); nothing advances.  After the native call(s) made with it
+        the caller sets `step_count = hp.step` — a call that was refused leaves the step number with the moments."""
+        g = self.param_groups[0]
+        return self._eng.hyper(gamma, alpha, inv_batch, self.step_count + 1, g["lr"], g["betas"], g["eps"])
+
+    _dueling = None      # _DuelingHeads of a DuelingQNetwork trainer: the heads' moments live beside the engine's
 
     def _moments(self):
         ms, vs = self._eng.views(self._eng.adam_m), self._eng.views(self._eng.adam_v)
@@ -429,6 +135,43 @@ class _FlatAdam:
         g = {k: v for k, v in self.param_groups[0].items() if k != "params"}
         g["params"] = list(range(len(self._params)))
         return dict(state=state, param_groups=[g])
+
+
+def read_losses(trainer, penalty=False):
+    """[loss, td_loss, cql_penalty] of the step just launched on trainer._engine: the device view with async_losses, else
+    one read-back that returns the loss and keeps last_td_loss (and, with `penalty`, last_cql_penalty)."""
+    stats = trainer._engine.stats[:3]
+    if trainer.async_losses:
+        return stats
+    loss, trainer.last_td_loss, pen = stats.tolist()
+    if penalty:
+        trainer.last_cql_penalty = pen
+    return loss
+
+
+def checked_loss(loss, actions, n_actions):
+    """`loss` (a float) — or the reference's IndexError: its `gather` raises on a minibatch with an action outside
+    0..A-1 (qr_dqn_trainer.py:147, c51_trainer.py:155); the loss-head kernels make no access through a bad index, the row
+    gets a NaN loss term and no gradient.  `actions`: callable giving the minibatch's actions, called only on a NaN."""
+    if loss != loss:
+        a = actions()
+        if not bool(((a >= 0) & (a < n_actions)).all()):
+            raise IndexError("action index out of range in the minibatch (valid: 0..%d)" % (n_actions - 1))
+    return loss
+
+
+def learn_minibatch(eng, opt, gamma, alpha, batch, variant):
+    """One step of `eng` on an explicit minibatch (device tensors): the step kernel on rows 0..B-1 of the minibatch
+    itself (learn_indexed, so every QnetVariant applies).  Returns the engine's statistics."""
+    states, actions, rewards, next_states, dones = batch
+    states, next_states = eng._states(states).contiguous(), eng._states(next_states, "next_states").contiguous()
+    B = states.shape[0]
+    hp = opt.hyper(gamma, alpha, 1.0 / B)
+    idx = torch.arange(B, dtype=torch.int64, device=eng.device)
+    eng.learn_indexed(hp, states, actions.long().contiguous(), rewards.float().contiguous(), next_states,
+                      dones.float().contiguous(), idx, variant=variant)
+    opt.step_count = hp.step
+    return eng.stats
 
 
 class CQLTrainer:
@@ -451,16 +194,11 @@ class CQLTrainer:
             raise NotImplementedError("QNetwork (a plain Linear/ReLU chain) and DuelingQNetwork are on the accelerated path")
         hidden = self.q_network._spec[2]
         self._engine = QnetEngine(state_size, action_size, hidden, max(max_batch, batch_size), self.device)
-        with torch.no_grad():
-            for mod, flat, which in ((self.q_network, self._engine.params, 0),
-                                     (self.target_network, self._engine.params_tgt, 1)):
-                # dueling: `model` holds the hidden layers only; the engine's output layer is the composed layer
-                owned = list(mod.model.parameters()) if dueling else list(mod.parameters())
-                for p, v in zip(owned, self._engine.views(flat)):
-                    v.copy_(p)
-                    p.data = v
-                mod._engine, mod._which = self._engine, which
-            if not dueling:
+        for which, mod in enumerate((self.q_network, self.target_network)):
+            # dueling: `model` holds the hidden layers only; the engine's output layer is the composed layer
+            self._engine.adopt(mod, which, list(mod.model.parameters()) if dueling else None)
+        if not dueling:
+            with torch.no_grad():
                 self._engine.params_tgt.copy_(self._engine.params)   # target.load_state_dict(q.state_dict())
         self._dueling = None
         if dueling:
@@ -489,10 +227,7 @@ class CQLTrainer:
         """cql_trainer.py:94-124 on an explicit minibatch (device tensors)."""
         eng, ex = self._engine, self._exchange
         B = eng.load_batch(states, actions, rewards, next_states, dones)
-        self.optimizer.step_count += 1
-        g = self.optimizer.param_groups[0]
-        hp = eng.hyper(self.gamma, float(self.alpha), 1.0 / (B * ex.world_size), self.optimizer.step_count,
-                       g["lr"], g["betas"], g["eps"])
+        hp = self.optimizer.hyper(self.gamma, float(self.alpha), 1.0 / (B * ex.world_size))
         if not ex.active:
             eng.learn(hp)
         else:
@@ -500,10 +235,8 @@ class CQLTrainer:
             ex.allreduce_sum_(eng.grads)
             ex.allreduce_sum_(eng.stats[:3])
             eng.apply(hp)
-        if self.async_losses:
-            return eng.stats[:3]
-        loss, self.last_td_loss, self.last_cql_penalty = eng.stats[:3].tolist()
-        return loss
+        self.optimizer.step_count = hp.step
+        return read_losses(self, penalty=True)
 
     def learn(self):
         return self.learn_on(*self.replay_buffer.sample(self.batch_size))
@@ -513,12 +246,10 @@ class CQLTrainer:
     def _learn_rows(self, idx):
         """learn_on on rows `idx` (device int64) of the replay mirror, gathered inside the step kernel."""
         eng, m = self._engine, self.replay_buffer._mirror
-        self.optimizer.step_count += 1
-        g = self.optimizer.param_groups[0]
-        hp = eng.hyper(self.gamma, float(self.alpha), 1.0 / idx.numel(), self.optimizer.step_count, g["lr"], g["betas"],
-                       g["eps"])
+        hp = self.optimizer.hyper(self.gamma, float(self.alpha), 1.0 / idx.numel())
         eng.learn_indexed(hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"], idx,
                           variant=self._rows_variant())
+        self.optimizer.step_count = hp.step
 
     def _rows_variant(self):
         return None
@@ -526,7 +257,6 @@ class CQLTrainer:
     def learn_device_sampled(self, seed=0):
         """Extension (not in the reference): `learn()` with the B distinct indices drawn on the device (keyed
         permutation) instead of numpy's O(N) host permutation — no host work, no host->device copies."""
-        from .. import engine as E
         rb = self.replay_buffer
         if self.batch_size > rb.size:
             raise ValueError("Cannot take a larger sample than population when 'replace=False'")
@@ -540,20 +270,15 @@ class CQLTrainer:
             return self.learn_on(*rb.gather_device(idx))
         # one-launch path: the step kernel draws the rows itself (or gathers rows idx of the device mirror)
         m = rb._mirror
-        self.optimizer.step_count += 1
-        g = self.optimizer.param_groups[0]
-        hp = eng.hyper(self.gamma, float(self.alpha), 1.0 / self.batch_size, self.optimizer.step_count, g["lr"], g["betas"],
-                       g["eps"])
+        hp = self.optimizer.hyper(self.gamma, float(self.alpha), 1.0 / self.batch_size)
         if eng.can_sample:
             eng.learn_sampled(hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"], rb.size,
                               self.batch_size, seed, draw)
         else:
             idx = E.sample_indices(rb.size, self.batch_size, seed, draw, device=self.device)
             eng.learn_indexed(hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"], idx)
-        if self.async_losses:
-            return eng.stats[:3]
-        loss, self.last_td_loss, self.last_cql_penalty = eng.stats[:3].tolist()
-        return loss
+        self.optimizer.step_count = hp.step
+        return read_losses(self, penalty=True)
 
     def compute_cql_penalty(self, states, actions):
         return self._engine.penalty(states, actions)
@@ -562,20 +287,11 @@ class CQLTrainer:
         self._engine.sync_target()
 
     def train_offline(self, policy=None, num_iterations: int = 10000):
-        losses = []
-        for self.training_step in range(num_iterations):
-            loss = self.learn() if policy is None else policy()
-            self.logger.log_loss(self.training_step, loss)
-            if self.training_step % self.update_target_freq == 0:      # dqn_trainer.py:195-196
-                self.sync_target()
-            losses.append(loss)
-        self.logger.close()
-        return losses
+        return online.run_offline(self, policy, num_iterations)
 
     def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
         """dqn_trainer.py:119-180 (train/online.py): learns once len(replay_buffer) >= training_learning_step; greedy
         actions, pushes and learn steps take the one-launch forms when the network and buffer allow."""
-        from . import online
         fast = None
         cls = type(self)
         if online.fast_ok(self) and cls._act_for is cls.select_action and cls._greedy_for is cls.get_action:

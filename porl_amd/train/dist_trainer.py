@@ -3,8 +3,11 @@
     sample (reference index stream) -> load -> online forward on s (activations kept) -> forward passes on s' ->
     loss head kernel (csrc/dist_losses.hpp: dL/d(output) + per-row loss) -> backward -> Adam
 
-Every arithmetic step is a HIP kernel behind the C ABI (porl_qnet_forward_loaded / porl_qr_loss / porl_c51_loss /
-porl_qnet_backward / porl_qnet_apply / porl_reduce_mean).  The output layer is wider than the one-launch step kernel's
+Every arithmetic step is a HIP kernel behind the C ABI.  The calls on the engine's handle (porl_qnet_forward_loaded /
+porl_qnet_backward / porl_qnet_apply / porl_qnet_dist_learn) are methods of engine.QnetEngine, which also checks the
+replay arrays (engine.replay_args); only the stateless loss heads (porl_qr_loss / porl_c51_loss / porl_reduce_mean) are
+called from the trainers.  The Adam step number advances after the native call that used it (cql_trainer._FlatAdam.hyper),
+and the reference's IndexError on a bad action is cql_trainer.checked_loss.  The output layer is wider than the one-launch step kernel's
 128 columns (actions x quantiles), so these trainers use the grouped-GEMM path like any wide Q-network.
 
 `learn_indexed(idx)` is the same step on rows `idx` of the replay mirror from ONE native call (porl_qnet_dist_learn:
@@ -13,8 +16,6 @@ Adam) — bit-equal parameters, moments and loss, no copies between the stages; 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -22,7 +23,9 @@ from .. import _native as N
 from ..buffer.replay_buffer import ReplayBuffer
 from ..parallel import GradExchange
 from ..utils.logger import Logger
-from .cql_trainer import QnetEngine, _FlatAdam
+from ..engine import QnetEngine
+from . import online
+from .cql_trainer import _FlatAdam, checked_loss
 
 
 class DistTrainerBase:
@@ -39,12 +42,9 @@ class DistTrainerBase:
         self.q_network, self.target_network = q_network, target_network
         s, n_out, hidden = q_network._spec
         self._engine = eng = QnetEngine(s, n_out, hidden, max(max_batch, batch_size), self.device)
+        eng.adopt(q_network, 0)
+        eng.adopt(target_network, 1)
         with torch.no_grad():
-            for mod, flat, which in ((q_network, eng.params, 0), (target_network, eng.params_tgt, 1)):
-                for p, v in zip(mod.parameters(), eng.views(flat)):
-                    v.copy_(p)
-                    p.data = v
-                mod._engine, mod._which = eng, which
             eng.params_tgt.copy_(eng.params)                           # target.load_state_dict(q.state_dict())
         target_network.eval()
         self.optimizer = _FlatAdam(eng, list(q_network.parameters()), learning_rate)
@@ -61,29 +61,17 @@ class DistTrainerBase:
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
 
     # -- engine pieces ----------------------------------------------------------------------------------
-    def _forward_loaded(self, which_params, which_input, keep, out):
-        eng = self._engine
-        N.check(eng._lib.porl_qnet_forward_loaded(eng._h, which_params, which_input, int(keep), N.ptr(out), out.stride(0),
-                                                  N.current_stream_ptr(eng.device)), "porl_qnet_forward_loaded")
-        return out
-
     def _backward_and_step(self, dout, B):
         eng = self._engine
-        N.check(eng._lib.porl_qnet_backward(eng._h, N.ptr(dout), dout.stride(0), N.current_stream_ptr(eng.device)),
-                "porl_qnet_backward")
-        self.optimizer.step_count += 1
-        g = self.optimizer.param_groups[0]
-        eng.apply(eng.hyper(self.gamma, 0.0, 1.0 / B, self.optimizer.step_count, g["lr"], g["betas"], g["eps"]))
-        N.check(eng._lib.porl_reduce_mean(N.ptr(self._row_loss), B, N.ptr(self._loss), N.current_stream_ptr(eng.device)),
+        eng.backward(dout)
+        hp = self.optimizer.hyper(self.gamma, 0.0, 1.0 / B)
+        eng.apply(hp)
+        self.optimizer.step_count = hp.step
+        N.check(N.lib().porl_reduce_mean(N.ptr(self._row_loss), B, N.ptr(self._loss), N.current_stream_ptr(eng.device)),
                 "porl_reduce_mean")
         if self.async_losses:
             return self._loss
-        loss = float(self._loss)
-        if loss != loss and not bool(((self._actions >= 0) & (self._actions < self.action_size)).all()):
-            # the reference's `gather` raises on such a batch (qr_dqn_trainer.py:147, c51_trainer.py:155); the loss-head
-            # kernels make no access through a bad index — the row gets a NaN loss term and no gradient
-            raise IndexError("action index out of range in the minibatch (valid: 0..%d)" % (self.action_size - 1))
-        return loss
+        return checked_loss(float(self._loss), lambda: self._actions, self.action_size)
 
     def _load(self, batch):
         states, actions, rewards, next_states, dones = batch
@@ -104,26 +92,9 @@ class DistTrainerBase:
     def _learn_rows(self, idx):
         """Launch learn_on on rows `idx` (device int64) of the replay mirror; the mean loss lands in eng.stats[0]."""
         eng, m = self._engine, self.replay_buffer._mirror
-        eng._ensure_bound()
-        B = idx.numel()
-        if B < 1 or B > eng.cfg.max_batch:
-            raise RuntimeError(f"batch {B} outside [1, {eng.cfg.max_batch}]")
-        if idx.dtype != torch.int64 or idx.device != eng.device or not idx.is_contiguous():
-            raise RuntimeError(f"idx: need a contiguous int64 tensor on {eng.device}")
-        for k, dt in (("states", torch.float32), ("next_states", torch.float32), ("actions", torch.int64),
-                      ("rewards", torch.float32), ("dones", torch.float32)):
-            if m[k].dtype != dt or m[k].device != eng.device or not m[k].is_contiguous():
-                raise RuntimeError(f"mirror {k}: need a contiguous {dt} tensor on {eng.device}")
-        S = eng.cfg.state_dim
-        if m["states"].shape[1:].numel() != S or m["next_states"].shape != m["states"].shape:
-            raise RuntimeError("replay arrays do not match the network's state_dim")
-        g = self.optimizer.param_groups[0]
-        hp = eng.hyper(self.gamma, 0.0, 1.0 / B, self.optimizer.step_count + 1, g["lr"], g["betas"], g["eps"])
-        head = self._dist_head()
-        N.check(eng._lib.porl_qnet_dist_learn(eng._h, N.ptr(m["states"]), S, N.ptr(m["actions"]), N.ptr(m["rewards"]),
-                                              N.ptr(m["next_states"]), S, N.ptr(m["dones"]), N.ptr(idx), B, C.byref(hp),
-                                              C.byref(head), N.current_stream_ptr(eng.device)), "porl_qnet_dist_learn")
-        self.optimizer.step_count += 1
+        hp = self.optimizer.hyper(self.gamma, 0.0, 1.0 / max(idx.numel(), 1))      # (an empty idx is the engine's to refuse)
+        eng.dist_learn(hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"], idx, self._dist_head())
+        self.optimizer.step_count = hp.step
 
     def learn_indexed(self, idx):
         """learn_on(*replay_buffer.sample_at(idx)) from one native call: same parameters, Adam moments and loss, bit for
@@ -137,12 +108,7 @@ class DistTrainerBase:
         stats = self._engine.stats
         if self.async_losses:
             return stats[:1]
-        loss = float(stats[0])
-        if loss != loss:
-            a = self.replay_buffer._mirror["actions"][idx]
-            if not bool(((a >= 0) & (a < self.action_size)).all()):              # learn_on's rule (_backward_and_step)
-                raise IndexError("action index out of range in the minibatch (valid: 0..%d)" % (self.action_size - 1))
-        return loss
+        return checked_loss(float(stats[0]), lambda: self.replay_buffer._mirror["actions"][idx], self.action_size)
 
     def sync_target(self):
         self._engine.sync_target()
@@ -171,7 +137,6 @@ class DistTrainerBase:
         network fits the act kernel, and the learn step runs from one native call on the sampled rows of the mirror
         (_learn_rows; its loss is read with the next act record) unless a subclass overrides learn / learn_on or a
         gradient exchange is active — then learn() as it stands."""
-        from . import online
         fast = None
         cls = type(self)
         if online.fast_ok(self) and cls._act_for is cls.select_action:

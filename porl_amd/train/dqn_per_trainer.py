@@ -12,7 +12,8 @@ import torch
 
 from .. import _native as N
 from ..buffer.prioritized_replay_buffer import PrioritizedReplayBuffer
-from .cql_trainer import CQLTrainer
+from . import online
+from .cql_trainer import CQLTrainer, read_losses
 
 
 class PERTrainer(CQLTrainer):
@@ -39,9 +40,7 @@ class PERTrainer(CQLTrainer):
         del states, actions, rewards, next_states, dones
         slots = (tree_idx - (mem.capacity - 1)).contiguous()
         st = mem._store
-        self.optimizer.step_count += 1
-        g = self.optimizer.param_groups[0]
-        hp = eng.hyper(self.gamma, 0.0, 1.0 / B, self.optimizer.step_count, g["lr"], g["betas"], g["eps"])
+        hp = self.optimizer.hyper(self.gamma, 0.0, 1.0 / B)
         td_abs = self._td_abs[:B]
         if self.per_sample_weights:
             var = N.QnetVariant(1, is_w.data_ptr(), None, td_abs.data_ptr())
@@ -50,18 +49,15 @@ class PERTrainer(CQLTrainer):
             var = N.QnetVariant(1, None, wmean.data_ptr(), td_abs.data_ptr())
         eng.learn_indexed(hp, st["states"], st["actions"], st["rewards"].view(-1), st["next_states"], st["dones"].view(-1),
                           slots, variant=var)
+        self.optimizer.step_count = hp.step
         mem.update_priorities(tree_idx, td_abs)
-        if self.async_losses:
-            return eng.stats[:3]
-        loss, self.last_td_loss, _ = eng.stats[:3].tolist()
-        return loss
+        return read_losses(self)
 
     def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
         """dqn_per_trainer.py:127-175: memory.add(max_initial_priority, ...) and a learn step once len(memory) >=
         batch_size; the loop of train/online.py.  On the one-launch step kernel with this class's own learn /
         select_action / get_action, acting, adding, sampling and the priority write-back take their one-launch forms
         (online._FastPER); otherwise the loop runs on select_action / memory.add / learn."""
-        from . import online
         cls, fast = type(self), None
         if cls.learn is PERTrainer.learn and cls._act_for is cls.select_action and cls._greedy_for is cls.get_action and \
                 online.fast_per_ok(self):

@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 
 from .. import _native as N
-from .cql_trainer import CQLTrainer
+from .cql_trainer import CQLTrainer, learn_minibatch, read_losses
 
 
 class DQNTrainer(CQLTrainer):
@@ -30,21 +30,9 @@ class DDQNTrainer(DQNTrainer):
 
     def learn_on(self, states, actions, rewards, next_states, dones):
         """ddqn_trainer.py:58-99 on an explicit minibatch (device tensors)."""
-        eng = self._engine
-        states, next_states = eng._states(states), eng._states(next_states, "next_states")
-        B = states.shape[0]
-        actions = actions.long().contiguous()
-        rewards, dones = rewards.float().contiguous(), dones.float().contiguous()
-        self.optimizer.step_count += 1
-        g = self.optimizer.param_groups[0]
-        hp = eng.hyper(self.gamma, 0.0, 1.0 / B, self.optimizer.step_count, g["lr"], g["betas"], g["eps"])
-        idx = torch.arange(B, dtype=torch.int64, device=self.device)
-        var = N.QnetVariant(1, None, None, None)
-        eng.learn_indexed(hp, states.contiguous(), actions, rewards, next_states.contiguous(), dones, idx, variant=var)
-        if self.async_losses:
-            return eng.stats[:3]
-        loss, self.last_td_loss, _ = eng.stats[:3].tolist()
-        return loss
+        learn_minibatch(self._engine, self.optimizer, self.gamma, 0.0, (states, actions, rewards, next_states, dones),
+                        N.QnetVariant(1, None, None, None))
+        return read_losses(self)
 
     _rows_for = learn_on
 

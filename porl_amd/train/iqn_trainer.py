@@ -36,6 +36,8 @@ from .. import engine as E
 from ..buffer.replay_buffer import ReplayBuffer
 from ..net.iqn_network import IQNNetwork, SelectAction
 from ..utils.logger import Logger
+from . import online
+from .cql_trainer import checked_loss
 
 
 class _FlatAdam:
@@ -183,10 +185,7 @@ class IQNTrainer:
         N.check(lib.porl_reduce_mean(N.ptr(row_loss), B, N.ptr(self._loss), st), "porl_reduce_mean")
         if self.async_losses:
             return self._loss
-        loss = float(self._loss)
-        if loss != loss and not bool(((actions >= 0) & (actions < A)).all()):
-            raise IndexError("action index out of range in the minibatch (valid: 0..%d)" % (A - 1))    # upstream's gather raises
-        return loss
+        return checked_loss(float(self._loss), lambda: actions, A)
 
     # -- the same step / action from one native call (csrc/iqn_api.inc) ------------------------------------------------
     def _views_intact(self):
@@ -239,10 +238,10 @@ class IQNTrainer:
         rb._sync_mirror()
         m = rb._mirror
         o = self.optimizer
-        o.step_count += 1
         g = o.param_groups[0]
-        hp = eng.hyper(self.gamma, self.kappa, self.max_norm, o.step_count, g["lr"], g["betas"], g["eps"])
+        hp = eng.hyper(self.gamma, self.kappa, self.max_norm, o.step_count + 1, g["lr"], g["betas"], g["eps"])
         eng.learn(hp, m["states"], m["actions"], m["rewards"], m["next_states"], m["dones"], idx, tp, tpp)
+        o.step_count = hp.step                 # after the call: a refused one leaves the step number with the moments
         return eng
 
     def learn_indexed(self, idx, taus_prime=None, taus_double_prime=None):
@@ -253,12 +252,7 @@ class IQNTrainer:
         eng = self._learn_rows(idx, taus_prime, taus_double_prime)
         if self.async_losses:
             return eng.stats[:3]
-        loss = float(eng.stats[0])
-        if loss != loss:
-            a = self.replay_buffer._mirror["actions"][idx]
-            if not bool(((a >= 0) & (a < self.action_size)).all()):
-                raise IndexError("action index out of range in the minibatch (valid: 0..%d)" % (self.action_size - 1))
-        return loss
+        return checked_loss(float(eng.stats[0]), lambda: self.replay_buffer._mirror["actions"][idx], self.action_size)
 
     def _act(self, rec, state=None, row=None, taus=None, n_stats=0, array="states"):
         """Launch the greedy action into the record `rec` (not waited for): `state` inline, or row `row` of the replay
@@ -286,20 +280,11 @@ class IQNTrainer:
 
     def train_offline(self, policy=None, num_iterations: int = 10000):
         """dqn_trainer.py:182-204 (inherited by the reference's IQNTrainer)."""
-        losses = []
-        for self.training_step in range(num_iterations):
-            loss = self.learn() if policy is None else policy()
-            self.logger.log_loss(self.training_step, loss)
-            if self.training_step % self.update_target_freq == 0:
-                self.sync_target()
-            losses.append(loss)
-        self.logger.close()
-        return losses
+        return online.run_offline(self, policy, num_iterations)
 
     def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
         """dqn_trainer.py:119-180 (inherited by the reference's IQNTrainer) on this trainer's select_action (it samples
         its own quantile fractions), push and learn; learns once len(replay_buffer) >= training_learning_step."""
-        from . import online
         fast = online._FastIQN(self) if online.fast_iqn_ok(self) else None
         return online.run(self, env, policy, num_episodes, max_steps, self.training_learning_step, self.replay_buffer,
                           self.replay_buffer.push, fast=fast)

@@ -38,6 +38,12 @@ an MLP a QnetEngine covers, so the trainer's own IqnEngine (csrc/iqn_api.inc) st
     flat gradient buffer, clip, Adam; mean loss, gradient norm and clip coefficient in the engine's statistics.
 Everything else (user `policy` callables, subclasses that override learn / learn_on / select_action, networks too large
 for one workgroup) runs the reference loop on the trainer's own select_action / push / learn.
+
+Nothing here makes a ctypes call: the engines of porl_amd/engine.py (the one ctypes layer) do, and they check the replay
+arrays (engine.replay_args).  The three `fast_*_ok` tests share `_rows_fit` (memory class, device, row width); `_Fast`
+knows which engine `record` writes through and how an act record is read (`_read_action`), so the flavours only override
+what differs.  Learn steps advance the Adam step number after their native call (cql_trainer._FlatAdam.hyper).
+`run_offline` is train_offline of the CQL family and of IQNTrainer.
 """
 from __future__ import annotations
 
@@ -45,11 +51,16 @@ import numpy as np
 import torch
 
 from .. import _native as N
+from ..buffer.prioritized_replay_buffer import PrioritizedReplayBuffer
+from ..buffer.replay_buffer import ReplayBuffer
+from ..engine import IqnEngine, QnetEngine, _norm_device
+from ..net.iqn_network import IQNNetwork
 
 
 class _Fast:
     def __init__(self, trainer, kind=0, n_sub=1, support=None, learn_rows=None, memory=None, engine=None):
         self.t, self.eng = trainer, trainer._engine if engine is None else engine
+        self.rec_eng = getattr(trainer, "_engine", None)     # the QnetEngine `record` writes through (None: the buffer's own)
         self.rb = trainer.replay_buffer if memory is None else memory
         self.kind, self.n_sub, self.support = kind, n_sub, support
         self.n_act = trainer.action_size
@@ -86,6 +97,10 @@ class _Fast:
             eng.act(self.rec, states=self._next_states(), row=self.state_row, **kw)
         else:
             eng.act(self.rec, inline=np.asarray(state, dtype=np.float32).reshape(-1), **kw)
+        return self._read_action(n_stats)
+
+    def _read_action(self, n_stats):
+        """Wait for the act record just launched: the action, and with it (n_stats) the newest learn step's loss."""
         self.stream.synchronize()
         if n_stats:
             self.resolve(float(self.rec_f[8]))
@@ -104,7 +119,7 @@ class _Fast:
 
     def push(self, state, action, reward, next_state, done):
         p = self.rb.position
-        self.state_row = p if self.rb.record(state, action, reward, next_state, done, engine=self.eng) else None
+        self.state_row = p if self.rb.record(state, action, reward, next_state, done, engine=self.rec_eng) else None
 
     # -- learning -----------------------------------------------------------------------------------------------------
     def learn(self):
@@ -183,15 +198,14 @@ class _FastPER(_Fast):
         if self.views is None:
             st = mem._store
             self.views = (st["states"], st["actions"], st["rewards"].view(-1), st["next_states"], st["dones"].view(-1))
-        t.optimizer.step_count += 1
-        g = t.optimizer.param_groups[0]
-        hp = eng.hyper(t.gamma, 0.0, 1.0 / B, t.optimizer.step_count, g["lr"], g["betas"], g["eps"])
+        hp = t.optimizer.hyper(t.gamma, 0.0, 1.0 / B)
         td_abs = t._td_abs[:B]
         if t.per_sample_weights:
             var = N.QnetVariant(1, is_w.data_ptr(), None, td_abs.data_ptr())
         else:
             var = N.QnetVariant(1, None, wmean.data_ptr(), td_abs.data_ptr())
         eng.learn_indexed(hp, *self.views, slots, variant=var)
+        t.optimizer.step_count = hp.step
         mem.update_priorities_device(tree_idx, td_abs)
         return self._deferred_loss()
 
@@ -215,14 +229,7 @@ class _FastIQN(_Fast):
         n_stats = 1 if self.in_stats is not None else 0
         self.t._act(self.rec, state=state if self.state_row is None else None, row=self.state_row, n_stats=n_stats,
                     array="next_states")
-        self.stream.synchronize()
-        if n_stats:
-            self.resolve(float(self.rec_f[8]))
-        return int(self.rec[0])
-
-    def push(self, state, action, reward, next_state, done):
-        p = self.rb.position
-        self.state_row = p if self.rb.record(state, action, reward, next_state, done) else None
+        return self._read_action(n_stats)
 
     def learn(self):
         self.eng = self.t._native_engine()         # (the same engine unless a larger one had to be made)
@@ -295,18 +302,37 @@ def run(trainer, env, policy, num_episodes, max_steps, threshold, memory, push, 
     return rewards_history
 
 
+def run_offline(trainer, policy=None, num_iterations: int = 10000):
+    """dqn_trainer.py:182-204: `num_iterations` learn steps (or calls of `policy`), each loss logged, the target network
+    synchronised every update_target_freq steps (dqn_trainer.py:195-196)."""
+    t = trainer
+    losses = []
+    for t.training_step in range(num_iterations):
+        loss = t.learn() if policy is None else policy()
+        t.logger.log_loss(t.training_step, loss)
+        if t.training_step % t.update_target_freq == 0:
+            t.sync_target()
+        losses.append(loss)
+    t.logger.close()
+    return losses
+
+
+def _rows_fit(memory, cls, device, S, max_inline):
+    """What the fast paths ask of the memory: exactly `cls`, on the HIP device `device`, its rows the network's S floats
+    and within what the record kernel and an inline act launch carry in their arguments."""
+    device = _norm_device(device)
+    return device.type == "cuda" and type(memory) is cls and _norm_device(memory.device) == device and \
+        memory.state_shape is not None and int(np.prod(memory.state_shape)) == S and \
+        S <= QnetEngine.RECORD_MAX_STATE and S <= max_inline
+
+
 def fast_per_ok(trainer):
     """The one-launch PER path applies: the trainer's own learn() on the one-launch step kernel, a network the act
     kernel covers, a device PrioritizedReplayBuffer whose rows fit the record kernel, no gradient exchange."""
-    from ..buffer.prioritized_replay_buffer import PrioritizedReplayBuffer
-    from ..engine import _norm_device
-    eng, mem = getattr(trainer, "_engine", None), trainer.memory
-    if eng is None or eng.device.type != "cuda" or type(mem) is not PrioritizedReplayBuffer or \
-            _norm_device(mem.device) != eng.device or trainer._exchange.active:
-        return False
-    S = eng.cfg.state_dim
-    if mem.state_shape is None or int(np.prod(mem.state_shape)) != S or \
-            S > eng.RECORD_MAX_STATE or S > eng.ACT_MAX_INLINE or trainer.batch_size > trainer._td_abs.numel():
+    eng = getattr(trainer, "_engine", None)
+    if eng is None or not _rows_fit(trainer.memory, PrioritizedReplayBuffer, eng.device, eng.cfg.state_dim,
+                                    eng.ACT_MAX_INLINE) or \
+            trainer._exchange.active or trainer.batch_size > trainer._td_abs.numel():
         return False
     eng._ensure_bound()
     return eng.fused and eng.act_ok
@@ -315,14 +341,8 @@ def fast_per_ok(trainer):
 def fast_ok(trainer):
     """The one-launch path applies: a QnetEngine on a HIP device behind a device-mirrored ReplayBuffer whose rows fit
     the record kernel, and a network the act kernel covers."""
-    from ..buffer.replay_buffer import ReplayBuffer
-    from ..engine import _norm_device
     eng = getattr(trainer, "_engine", None)
-    rb = trainer.replay_buffer
-    if eng is None or eng.device.type != "cuda" or type(rb) is not ReplayBuffer or _norm_device(rb.device) != eng.device:
-        return False
-    S = int(np.prod(rb.state_shape))
-    if S != eng.cfg.state_dim or S > eng.RECORD_MAX_STATE or S > eng.ACT_MAX_INLINE:
+    if eng is None or not _rows_fit(trainer.replay_buffer, ReplayBuffer, eng.device, eng.cfg.state_dim, eng.ACT_MAX_INLINE):
         return False
     eng._ensure_bound()
     return eng.act_ok
@@ -332,23 +352,15 @@ def fast_iqn_ok(trainer):
     """The native IQN path applies: a HIP device, the device-mirrored ReplayBuffer with rows that fit the record and
     inline limits, both networks exactly IQNNetwork on the trainer's flat buffers, learn / learn_on / select_action not
     overridden, sizes within the engine's limits."""
-    from ..buffer.replay_buffer import ReplayBuffer
-    from ..engine import IqnEngine, _norm_device
-    from ..net.iqn_network import IQNNetwork
-    from ..train.cql_trainer import QnetEngine
     from .iqn_trainer import IQNTrainer
-    t, rb = trainer, trainer.replay_buffer
-    dev = _norm_device(t.device)
-    if dev.type != "cuda" or type(rb) is not ReplayBuffer or _norm_device(rb.device) != dev:
+    t = trainer
+    if not _rows_fit(t.replay_buffer, ReplayBuffer, t.device, t.state_size, IqnEngine.ACT_MAX_INLINE):
         return False
     if type(t.q_network) is not IQNNetwork or type(t.target_network) is not IQNNetwork:
         return False
     cls = type(t)
     if cls.learn is not IQNTrainer.learn or cls.learn_on is not IQNTrainer.learn_on or \
             cls.select_action is not IQNTrainer.select_action:
-        return False
-    S = int(np.prod(rb.state_shape))
-    if S != t.state_size or S > QnetEngine.RECORD_MAX_STATE or S > IqnEngine.ACT_MAX_INLINE:
         return False
     q = t.q_network
     if q.embedding_dim != t.embedding_dim or q.embedding_dim > IqnEngine.MAX_EMBED or t.action_size > IqnEngine.MAX_ACTIONS or \

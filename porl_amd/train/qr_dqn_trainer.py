@@ -30,14 +30,14 @@ class QRDQNTrainer(DistTrainerBase):
 
     def learn_on(self, states, actions, rewards, next_states, dones):
         B, actions, rewards, dones = self._load((states, actions, rewards, next_states, dones))
-        z_cur = self._forward_loaded(0, 0, True, self._out[0][:B])
-        z_no = self._forward_loaded(0, 1, False, self._out[1][:B])
-        z_nt = self._forward_loaded(1, 1, False, self._out[2][:B])
+        z_cur = self._engine.forward_loaded(0, 0, True, self._out[0][:B])
+        z_no = self._engine.forward_loaded(0, 1, False, self._out[1][:B])
+        z_nt = self._engine.forward_loaded(1, 1, False, self._out[2][:B])
         dz = self._dout[:B]
-        N.check(self._engine._lib.porl_qr_loss(N.ptr(z_cur), N.ptr(z_no), N.ptr(z_nt), z_cur.stride(0), N.ptr(actions),
-                                               N.ptr(rewards), N.ptr(dones), B, self.action_size, self.num_quantiles,
-                                               self.gamma, self.kappa, N.ptr(dz), N.ptr(self._row_loss),
-                                               N.current_stream_ptr(self.device)), "porl_qr_loss")
+        N.check(N.lib().porl_qr_loss(N.ptr(z_cur), N.ptr(z_no), N.ptr(z_nt), z_cur.stride(0), N.ptr(actions),
+                                     N.ptr(rewards), N.ptr(dones), B, self.action_size, self.num_quantiles,
+                                     self.gamma, self.kappa, N.ptr(dz), N.ptr(self._row_loss),
+                                     N.current_stream_ptr(self.device)), "porl_qr_loss")
         return self._backward_and_step(dz, B)
 
     _rows_for = learn_on

@@ -257,7 +257,7 @@ def test_sampled_calls_are_unsupported_without_in_kernel_sampling():
     with pytest.raises(N.NativeError, match=r"rc=-2"):
         eng.bcq_learn_sampled(beh, hp, *args, n_rows, B, 0, 0, 0.17)
     with pytest.raises(N.NativeError, match=r"rc=-2"):
-        beh.learn_sampled_variant(hp, *args, n_rows, B, 0, 0, N.QnetVariant(0, None, None, None, None, 1))
+        beh.learn_sampled(hp, *args, n_rows, B, 0, 0, variant=N.QnetVariant(0, None, None, None, None, 1))
     torch.cuda.synchronize()
     assert torch.equal(eng.params, before[0]) and torch.equal(beh.params, before[1])
     # the Python forms take the indexed route and equal the existing pieces on the same draws

@@ -6,6 +6,7 @@ import ctypes as C
 import os
 
 import pytest
+import torch
 
 from conftest import GOLDEN, load_golden
 from porl_amd import _native as N
@@ -50,6 +51,11 @@ def test_dist_learn_rejects_a_null_and_an_unbound_engine():
     _rejected(call(None), "null engine")
     eng = QnetEngine(8, 48, [16], 4, "cpu")               # created, never bound
     _rejected(call(eng._h), "porl_qnet_bind")
+    # the engine's own methods refuse a CPU engine in _ensure_bound, before they look at any argument
+    for method, args in ((eng.dist_learn, (hp, None, None, None, None, None, torch.zeros(4, dtype=torch.int64), head)),
+                         (eng.forward_loaded, (0, 0, True, None)), (eng.backward, (None,))):
+        with pytest.raises(N.NativeError, match="no CPU path"):
+            method(*args)
 
 
 def test_trainers_name_the_learn_on_their_one_call_step_reproduces():

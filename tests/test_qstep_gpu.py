@@ -246,7 +246,7 @@ def test_td_abs_is_optional_and_written_nowhere_else(form, name):
 @pytest.mark.parametrize("B", [1, 33])
 @pytest.mark.parametrize("var", ["cql", "per"])
 def test_in_kernel_sampler_on_ragged_batches(var, B):
-    """learn_sampled / learn_sampled_variant on a batch that does not fill its last block: bit-equal to learn_indexed on the
+    """learn_sampled (with and without a variant) on a batch that does not fill its last block: bit-equal to learn_indexed on the
     rows engine.sample_indices gives; is_w and td_abs are indexed by minibatch position."""
     from porl_amd import engine as E
     d, _, _ = _ref(f"{'row1' if B == 1 else 'odd'}-a5-{var}")
@@ -266,10 +266,8 @@ def test_in_kernel_sampler_on_ragged_batches(var, B):
             idx = E.sample_indices(n_rows, B, seed, draw, device=DEV)
             assert len(set(idx.tolist())) == B and 0 <= int(idx.min()) and int(idx.max()) < n_rows
             eng.learn_indexed(hp, *replay, idx, variant=var_)
-        elif var_ is None:
-            eng.learn_sampled(hp, *replay, n_rows, B, seed, draw)
         else:
-            eng.learn_sampled_variant(hp, *replay, n_rows, B, seed, draw, var_)
+            eng.learn_sampled(hp, *replay, n_rows, B, seed, draw, variant=var_)
         torch.cuda.synchronize()
         assert (td[B:] == SENTINEL).all()
         assert bool((td[:B] != SENTINEL).all()) == v["td_abs"]
