@@ -200,6 +200,46 @@ int porl_iql_step(porl_iql* h, const porl_iql_hyper* hp, void* stream);
 int porl_iql_policy_only_forward(porl_iql* h, const porl_iql_hyper* hp, void* stream);
 int porl_iql_policy_only_step(porl_iql* h, const porl_iql_hyper* hp, void* stream);
 
+/* Goal-conditioned behaviour cloning — the action policy pi(a | s, g) of POR and RvS, reference agent/por.py:178-183:
+ *     policy(concat([obs, goal], dim=1)),  mean(-log_prob(actions)),  Adam.
+ * The engine is created with cfg.obs_dim = S + G and cfg.pol_out_dim = A; its value nets are not used.
+ *
+ * The two loaders stage, in ONE launch (one wave per batch row), straight into the engine's staging buffers
+ *     input  row i = [ obs (S) | goal (G) | 0 padding ],   target row i = [ action (A) | 0 padding ],   weight i = 1.0f
+ * so there is no concatenated tensor and no staging copy, and the NLL kernel runs unchanged on unit weights.
+ *   porl_iql_load_batch_cat   : dense or strided tensors obs (batch, S = cfg.obs_dim - goal_dim), goals (batch, goal_dim),
+ *       actions (batch, cfg.pol_out_dim); *_rs are row strides in floats, columns have unit stride.
+ *   porl_iql_load_batch_pairs : rows of a packed store [s(state_dim) | r | s' | d | a(act_dim)].  Row `start` gives s and a,
+ *       row `goal` gives columns [goal_col, goal_col + goal_dim), which must lie in the state part of a row
+ *       (goal_col + goal_dim <= 2*state_dim + 2).  Which rows:
+ *         start and goal given (int64, batch each)  : those pairs; duplicates and goal == start are allowed;
+ *         start given, goal NULL                     : the goal row is the start row (goal_col = state_dim + 1: POR's [s | s']);
+ *         start NULL, ep_starts / ep_lengths given   : hindsight pairs drawn in the kernel with porl_hindsight_pairs' counter
+ *                                                      stream — the same (seed, step) gives its pairs, index for index;
+ *         start NULL, no table                       : `batch` distinct rows by the keyed permutation of
+ *                                                      porl_iql_load_batch_sampled (seed, step); goal row = start row.
+ *       start_out / goal_out (batch int64, optional) receive the rows used.  A row number outside [0, n_rows) is not
+ *       read: that batch row is staged as NaN (porl_gather_pairs' rule) and the loss comes out NaN.
+ * Both honour PORL_IQL_MODE_TWO_SLOTS.  Every argument is judged before the first device call.
+ *
+ *   porl_iql_bc_step    : por.py:178-183 on the staged batch — the policy net's hidden layers (one net per launch), mean,
+ *       NLL with the unit weights, the policy phase's gradient half, Adam with the combine folded in (2 L + 4 launches at
+ *       n_hidden = L).  Reads hp->policy_lr, policy_step, inv_batch and the Adam constants; writes params_pol, grads_pol,
+ *       adam_*_pol, stats[1] = the loss, stats[2] = min NLL; nothing of group 0, of the target net, or stats[0].
+ *   porl_iql_bc_forward : its forward half (up to NLL, dL/dmean and the loss partials); porl_iql_policy_backward on the
+ *       same batch completes it without an apply (grads_pol, stats[1], stats[2]) and porl_iql_policy_apply applies it.
+ * A goal-conditioned batch carries no next observations, rewards or flags: every other phase call on it returns
+ * PORL_ERR_INVALID and launches nothing, and so do the bc calls on a batch staged by any other loader. */
+int porl_iql_load_batch_cat(porl_iql* h, int32_t batch, const float* obs, int64_t obs_rs, const float* goals,
+                            int64_t goals_rs, int32_t goal_dim, const float* actions, int64_t act_rs, void* stream);
+int porl_iql_load_batch_pairs(porl_iql* h, int32_t batch, const float* rows, int64_t row_stride, int64_t n_rows,
+                              int32_t state_dim, int32_t act_dim, int32_t goal_col, int32_t goal_dim,
+                              const int64_t* start, const int64_t* goal, const int64_t* ep_starts,
+                              const int64_t* ep_lengths, int64_t n_episodes, uint64_t seed, uint64_t step,
+                              int64_t* start_out, int64_t* goal_out, void* stream);
+int porl_iql_bc_forward(porl_iql* h, const porl_iql_hyper* hp, void* stream);
+int porl_iql_bc_step(porl_iql* h, const porl_iql_hyper* hp, void* stream);
+
 /* Forward-only paths: TwinV.both (value_functions.py:38-39) on vf (which=0) or the target (which=1),
  * and the policy mean (policy.py:19 / sorl.py:71-76).  x is (batch, obs_dim) with row stride x_rs. */
 int porl_iql_forward_value(porl_iql* h, int which, const float* x, int64_t x_rs, int32_t batch,

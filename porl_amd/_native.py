@@ -22,6 +22,7 @@ SYMBOLS = [
     "porl_iql_adam_plan",
     "porl_iql_value_backward", "porl_iql_value_apply", "porl_iql_policy_forward", "porl_iql_policy_backward",
     "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_only_forward", "porl_iql_policy_only_step", "porl_iql_policy_prefetch", "porl_iql_forward_value", "porl_iql_forward_policy",
+    "porl_iql_load_batch_cat", "porl_iql_load_batch_pairs", "porl_iql_bc_forward", "porl_iql_bc_step",
     "porl_gemm_f32", "porl_gemm_f32_group", "porl_adam_ema", "porl_ema", "porl_softmax_mask", "porl_gather_rows", "porl_sample_indices", "porl_epoch_indices", "porl_per_update", "porl_per_sample",
     "porl_per_record", "porl_per_sample_slots", "porl_per_update_f32",
     "porl_prof_enable", "porl_prof_read", "porl_tune_set", "porl_tune_set_ptr", "porl_state2costmap", "porl_astar_label",
@@ -176,11 +177,15 @@ def _declare(lib):
     lib.porl_iql_load_batch.argtypes = [vp, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     lib.porl_iql_load_batch_sampled.argtypes = [vp, i32, vp, i64, i64, i32, i32, C.c_uint64, C.c_uint64, vp, vp]
     lib.porl_iql_load_batch_indexed.argtypes = [vp, i32, vp, i64, i64, vp, i32, i32, i32, i32, vp, i64, vp, i64, vp]
+    lib.porl_iql_load_batch_cat.argtypes = [vp, i32, vp, i64, vp, i64, i32, vp, i64, vp]
+    lib.porl_iql_load_batch_pairs.argtypes = [vp, i32, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, i64, C.c_uint64,
+                                              C.c_uint64, vp, vp, vp]
     lib.porl_iql_set_stats.argtypes = [vp, vp]
     lib.porl_iql_set_mode.argtypes = [vp, i32]
     lib.porl_iql_adam_plan.argtypes = [vp, C.c_int, C.POINTER(i32 * 6)]
     for name in ("porl_iql_value_backward", "porl_iql_value_apply", "porl_iql_policy_forward", "porl_iql_policy_backward",
-                 "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_only_forward", "porl_iql_policy_only_step"):
+                 "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_only_forward", "porl_iql_policy_only_step",
+                 "porl_iql_bc_forward", "porl_iql_bc_step"):
         getattr(lib, name).argtypes = [vp, C.POINTER(IqlHyper), vp]
     lib.porl_iql_policy_prefetch.argtypes = [vp, vp]
     lib.porl_iql_forward_value.argtypes = [vp, C.c_int, vp, i64, i32, vp, vp, vp]

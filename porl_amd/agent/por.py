@@ -10,9 +10,14 @@ mirror's scatter of newly pushed transitions (buffer/replay_buffer.py).
 
 Deliberate differences from the reference (SURVEY.md §8 notes 6):
   * the `pdb.set_trace()` on NLL <= 0 (por.py:104-105) becomes a one-time RuntimeWarning;
-  * dead upstream code (`pretrain*`, `por_qlearning_update`, `save/load`) is not provided;
+  * dead upstream code (`pretrain*`, `save/load`, and `por_qlearning_update` but for its action-policy block, which is
+    agent/goal_bc.py) is not provided;
   * with `backbone=FasterNet(...)` (por.py:46-57,75-79) the encoder runs forward-only: it joins no optimizer
     upstream, so its backward only fills gradients nobody reads.
+
+Acting (reference test.py:29 calls `agent.select_action`, which the reference's POR does not define): POR acts through a
+second policy pi(a | s, g) on [s | goal_policy mean(s)].  `set_execute_policy(bc)` takes a trained
+`porl_amd.agent.goal_bc.GoalConditionedBC` (por.py:178-184), `select_action(observations)` returns its mean action.
 
 Extension: `update_from_replay(replay, batch_size, indices=None)` runs the same step on rows of a device-resident
 `PackedReplay`, drawn on the device or named by `indices`, with or without a backbone; the store is only read.
@@ -94,3 +99,30 @@ class POR(IqlAgentBase):
         idx, feats = agent._replay_rows(replay, batch_size, indices)
         return agent._full_update(None, None, None, None, None, agent.v_optimizer, agent.goal_policy_optimizer,
                                   agent.goal_lr_schedule, replay=replay, batch=batch_size, idx=idx, feats=feats)
+
+    def set_execute_policy(agent, bc):
+        """The action policy pi(a | s, g) POR acts through: a `GoalConditionedBC` with obs_dim = goal_dim = state_size
+        (trained by its own `update` / `update_from_replay(goal="next")`).  It is held OUTSIDE the module registry: it
+        has its own engine, optimizer and checkpoint, and `POR.state_dict()` keeps the reference's keys."""
+        from .goal_bc import GoalConditionedBC
+        if not isinstance(bc, GoalConditionedBC):
+            raise TypeError(f"set_execute_policy: expected a GoalConditionedBC, got {type(bc).__name__}")
+        S = agent.goal_policy._spec[1]
+        if agent.backbone is not None or bc.obs_dim != agent.goal_policy._spec[0] or bc.goal_dim != S:
+            raise ValueError(f"set_execute_policy: the policy acts on [{bc.obs_dim} | {bc.goal_dim}] columns, a POR agent "
+                             f"without a backbone supplies [{S} | {S}]")
+        agent.__dict__["_execute_policy"] = bc
+
+    def select_action(agent, observations):
+        """What reference test.py:29 calls: the action policy's mean on [obs | goal_policy mean(obs)], as a numpy array.
+        `observations`: (state_size,) or (B, state_size), numpy or tensor; up to 8 rows take the host-memory path of both
+        policies (`GaussianPolicy.mean_numpy`)."""
+        bc = agent.__dict__.get("_execute_policy")
+        if bc is None:
+            raise RuntimeError("select_action: no action policy is set (POR.set_execute_policy)")
+        import numpy as np
+        if isinstance(observations, torch.Tensor):
+            observations = observations.detach().cpu().numpy()
+        observations = np.asarray(observations, dtype=np.float32)
+        goal = agent.goal_policy.mean_numpy(observations)
+        return bc.policy.mean_numpy(np.concatenate([observations, goal], axis=-1))

@@ -164,6 +164,35 @@ def build_sanitized_normalize(force=False, verbose=True):
     return SAN_NORMALIZE_DRIVER
 
 
+# sixth driver, built the same way: the goal-conditioned behaviour-cloning entry points (tests/test_goal_bc_host.py)
+SAN_GOAL_BC_DRIVER_SRC = os.path.join(os.path.dirname(HERE), "tests", "helpers", "abi_reject_goal_bc.cpp")
+SAN_GOAL_BC_DRIVER = os.path.join(HERE, "lib", "abi_reject_goal_bc_san")
+
+
+def build_sanitized_goal_bc(force=False, verbose=True):
+    """tests/helpers/abi_reject_goal_bc.cpp -> SAN_GOAL_BC_DRIVER, a stand-alone program linked against the host-only
+    sanitized library of `build_sanitized` (built first when it is not current).  Cached by the hash of the library's
+    sources and the driver's.  Returns SAN_GOAL_BC_DRIVER."""
+    import hashlib
+    build_sanitized(force=force, verbose=verbose)
+    h = hashlib.sha256((source_hash() + open(SAN_GOAL_BC_DRIVER_SRC).read()).encode()).hexdigest()
+    tag = SAN_GOAL_BC_DRIVER + ".srchash"
+    try:
+        if not force and os.path.exists(SAN_GOAL_BC_DRIVER) and open(tag).read().strip() == h:
+            return SAN_GOAL_BC_DRIVER
+    except OSError:
+        pass
+    clangxx = os.path.join(os.path.dirname(os.path.dirname(hipcc())), "lib", "llvm", "bin", "clang++")
+    cmd = [clangxx if os.path.exists(clangxx) else "clang++", "-std=c++17", "-O1", "-g", *SAN_FLAGS, "-o", SAN_GOAL_BC_DRIVER,
+           SAN_GOAL_BC_DRIVER_SRC, SAN_OUT, "-Wl,-rpath," + os.path.dirname(SAN_OUT)]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL if not verbose else None)
+    with open(tag, "w") as f:
+        f.write(h + "\n")
+    return SAN_GOAL_BC_DRIVER
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     print(OUT)
@@ -173,3 +202,4 @@ if __name__ == "__main__":
         print(SAN_EPISODES_DRIVER)
         print(build_sanitized_holdout(force="--force" in sys.argv))
         print(build_sanitized_normalize(force="--force" in sys.argv))
+        print(build_sanitized_goal_bc(force="--force" in sys.argv))

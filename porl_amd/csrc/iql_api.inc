@@ -13,7 +13,10 @@
 //   policy_mean_nll                   mean + NLL, the end of both forward halves
 //   value_adam / policy_adam          the two Adam launches
 //   iql_batch_loaded                  what every loader leaves behind
-//   iql_enter, check_batch, check_replay_rows, need_pol_target     the rejections; no HIP call comes before them
+//   iql_enter, check_batch, check_replay_rows, need_pol_target, need_kind     the rejections; no HIP call comes before them
+// The goal-conditioned behaviour-cloning step (porl_iql_bc_*, reference agent/por.py:178-183) is the policy phase on a
+// batch of its own kind: stage_pairs_kernel (pairs.hpp) stages [obs | goal], the actions and unit weights, then B1/B2 the
+// policy net's hidden layers alone, B3 mean, B4 NLL, P5..P7 the ordinary gradient half, B9 Adam.
 // Nothing here allocates per launch outside g_prof.on: small configurations are bound by host time.
 
 namespace {
@@ -79,6 +82,7 @@ struct porl_iql {
   int32_t adam_plan[2][6] = {};     // porl_iql_adam_plan: what the last Adam launch of each group did with its jobs
   int batch = 0;
   bool have_pol_target = false;
+  bool pair_batch = false;          // staged by porl_iql_load_batch_cat / _pairs: [obs | goal], actions, unit weights and nothing else
   bool pol_prefetched = false;      // porl_iql_policy_prefetch ran for the loaded batch: policy forward is done
   bool pol_fwd_done = false;        // porl_iql_policy_forward ran for the loaded batch
   int pol_nslab = 1;
@@ -120,11 +124,22 @@ int need_pol_target(const porl_iql* h) {
   if (!h->have_pol_target) PORL_FAIL(PORL_ERR_INVALID, "policy step needs pol_target in porl_iql_load_batch");
   return 0;
 }
+// A batch staged by porl_iql_load_batch_cat / _pairs carries no next observations, rewards or flags: only the bc calls
+// run on it, and they run on nothing else.
+int need_kind(const porl_iql* h, bool pairs, const char* who) {
+  if (h->pair_batch == pairs) return 0;
+  if (pairs)
+    PORL_FAIL(PORL_ERR_INVALID, "%s: the loaded batch was not staged by porl_iql_load_batch_cat / porl_iql_load_batch_pairs "
+              "(a goal-conditioned batch: [obs | goal], actions, unit weights)", who);
+  PORL_FAIL(PORL_ERR_INVALID, "%s: the loaded batch is a goal-conditioned one (porl_iql_load_batch_cat / porl_iql_load_batch_pairs): "
+            "it has no next observations, rewards or flags; only porl_iql_bc_step / porl_iql_bc_forward run on it", who);
+}
 
 // What a loader leaves behind once its kernel is enqueued: the batch and what is known about it.
-void iql_batch_loaded(porl_iql* h, int batch, bool have_target) {
+void iql_batch_loaded(porl_iql* h, int batch, bool have_target, bool pairs = false) {
   h->batch = batch;
   h->have_pol_target = have_target;
+  h->pair_batch = pairs;
   h->pol_prefetched = false;
   h->pol_fwd_done = false;
 }
@@ -639,6 +654,21 @@ int policy_only_forward_half(porl_iql* h, const porl_iql_hyper* hp, hipStream_t 
   return policy_mean_nll(h, hp, s, pre, parts, W + ws.pol_w, "O4.mean:", "O5.");
 }
 
+// Forward half of the behaviour-cloning step (porl_iql_bc_*, reference por.py:178-180): the policy net's hidden layers,
+// one net per launch as porl_iql_policy_prefetch issues them, then mean and NLL with the unit weights the loader staged.
+// No V net runs and no weight kernel: L + 2 launches.
+int bc_forward_half(porl_iql* h, const porl_iql_hyper* hp, hipStream_t s) {
+  const int S = h->cfg.obs_dim, H = h->cfg.hidden_dim, L = h->cfg.n_hidden;
+  h->pol_prefetched = false;
+  int parts = 0;
+  for (int l = 0; l < L; ++l) {
+    const FwdNet f = policy_fwd_net(h, l, h->ws.xs_slot[h->slot]);
+    g_phase = l == 0 ? "B1.L0fwd:" : "B2.fwd:";
+    PORL_TRY(fwd_hidden_layer(h, &f, 1, h->batch, l == 0 ? S : H, l == L - 1, &parts, true, s));
+  }
+  return policy_mean_nll(h, hp, s, false, 0, h->buf.workspace + h->ws.pol_w, "B3.mean:", "B4.");
+}
+
 // Gradient half: needs a forward half of the same batch (dL/dmean, the NLL partials, act_p).  Touches policy state only.
 int policy_gradient_half(porl_iql* h, hipStream_t s, ReduceArgs* defer) {
   const int B = h->batch, S = h->cfg.obs_dim, H = h->cfg.hidden_dim, L = h->cfg.n_hidden, D = h->cfg.pol_out_dim;
@@ -756,6 +786,26 @@ int small_fwd(int nnets, const float* const* Wt, const float* const* bias, const
   ProfScope ps("small_fwd_kernel", s, 2.0 * nnets * B * N * K, 4.0 * nnets * ((double)N * K + B * (N + K)));
   hipLaunchKernelGGL(small_fwd_kernel, dim3(std::min(cdiv(N, 4), 1024), nnets), dim3(256), lds, s, a);
   PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+// The one launch both goal-conditioned loaders end in.
+int stage_pairs(porl_iql* h, PairStageArgs& a, int batch, int S, int G, int A, int64_t* start_out, int64_t* goal_out,
+                void* stream) {
+  DevGuard _dg(h->device);
+  float* W = h->buf.workspace;
+  const int slot = next_slot(h);
+  a.batch = batch; a.S = S; a.G = G; a.A = A; a.Sp = h->Sp; a.Dp = h->Dp;
+  a.xs = W + h->ws.xs_slot[slot]; a.xt = W + h->ws.xt_slot[slot]; a.w = W + h->ws.pol_w;
+  a.start_out = reinterpret_cast<long long*>(start_out); a.goal_out = reinterpret_cast<long long*>(goal_out);
+  {
+    g_phase = "B0.";
+    ProfScope ps("stage_pairs_kernel", (hipStream_t)stream, 0.0, 8.0 * batch * (S + G + A + 1));
+    hipLaunchKernelGGL(stage_pairs_kernel, dim3(cdiv(batch, 4)), dim3(256), 0, (hipStream_t)stream, a);
+    g_phase = "";
+  }
+  PORL_HIP(hipGetLastError());
+  iql_batch_loaded(h, batch, true, true);
   return PORL_OK;
 }
 
@@ -988,9 +1038,76 @@ int porl_iql_load_batch_indexed(porl_iql* h, int32_t batch, const float* rows, i
   return PORL_OK;
 }
 
+int porl_iql_load_batch_cat(porl_iql* h, int32_t batch, const float* obs, int64_t obs_rs, const float* goals, int64_t goals_rs,
+                            int32_t goal_dim, const float* actions, int64_t act_rs, void* stream) {
+  PORL_TRY(check_ready(h, false));
+  PORL_TRY(check_batch(h, batch));
+  if (!obs) PORL_FAIL(PORL_ERR_INVALID, "null obs");
+  if (!goals) PORL_FAIL(PORL_ERR_INVALID, "null goals");
+  if (!actions) PORL_FAIL(PORL_ERR_INVALID, "null actions");
+  if (goal_dim < 1 || goal_dim >= h->cfg.obs_dim)
+    PORL_FAIL(PORL_ERR_INVALID, "goal_dim %d outside [1, obs_dim %d): the engine's input is [obs | goal]", goal_dim, h->cfg.obs_dim);
+  const int S = h->cfg.obs_dim - goal_dim, A = h->cfg.pol_out_dim;
+  if (batch > 1 && obs_rs < S) PORL_FAIL(PORL_ERR_INVALID, "obs_rs %lld below the %d observation columns", (long long)obs_rs, S);
+  if (batch > 1 && goals_rs < goal_dim) PORL_FAIL(PORL_ERR_INVALID, "goals_rs %lld below goal_dim %d", (long long)goals_rs, goal_dim);
+  if (batch > 1 && act_rs < A) PORL_FAIL(PORL_ERR_INVALID, "act_rs %lld below pol_out_dim %d", (long long)act_rs, A);
+  PairStageArgs a{};
+  a.mode = PAIR_DENSE; a.n_rows = batch;
+  a.s = PairSrc{obs, (long long)obs_rs, 0}; a.g = PairSrc{goals, (long long)goals_rs, 0}; a.a = PairSrc{actions, (long long)act_rs, 0};
+  return stage_pairs(h, a, batch, S, goal_dim, A, nullptr, nullptr, stream);
+}
+
+int porl_iql_load_batch_pairs(porl_iql* h, int32_t batch, const float* rows, int64_t row_stride, int64_t n_rows,
+                              int32_t state_dim, int32_t act_dim, int32_t goal_col, int32_t goal_dim, const int64_t* start,
+                              const int64_t* goal, const int64_t* ep_starts, const int64_t* ep_lengths, int64_t n_episodes,
+                              uint64_t seed, uint64_t step, int64_t* start_out, int64_t* goal_out, void* stream) {
+  PORL_TRY(check_ready(h, false));
+  PORL_TRY(check_batch(h, batch));
+  if (!rows) PORL_FAIL(PORL_ERR_INVALID, "null rows");
+  if (n_rows < 1 || n_rows > (int64_t(1) << 40)) PORL_FAIL(PORL_ERR_INVALID, "n_rows %lld outside [1, 2^40]", (long long)n_rows);
+  if (state_dim < 1 || act_dim < 1 || goal_dim < 1)
+    PORL_FAIL(PORL_ERR_INVALID, "state_dim %d / act_dim %d / goal_dim %d must be positive", state_dim, act_dim, goal_dim);
+  const int64_t S = state_dim, state_part = 2 * S + 2;
+  if (row_stride < state_part + act_dim || row_stride > (int64_t(1) << 26))
+    PORL_FAIL(PORL_ERR_INVALID, "row_stride %lld: a row is 2*state_dim+2+act_dim = %lld floats", (long long)row_stride,
+              (long long)(state_part + act_dim));
+  if (goal_col < 0) PORL_FAIL(PORL_ERR_INVALID, "goal_col %d must not be negative", goal_col);
+  if ((int64_t)goal_col + goal_dim > state_part)
+    PORL_FAIL(PORL_ERR_INVALID, "goal_col %d + goal_dim %d runs past the state part of a row (2*state_dim+2 = %lld)", goal_col,
+              goal_dim, (long long)state_part);
+  if (S + goal_dim != h->cfg.obs_dim)
+    PORL_FAIL(PORL_ERR_INVALID, "state_dim %d + goal_dim %d != obs_dim %d", state_dim, goal_dim, h->cfg.obs_dim);
+  if (act_dim != h->cfg.pol_out_dim) PORL_FAIL(PORL_ERR_INVALID, "act_dim %d != pol_out_dim %d", act_dim, h->cfg.pol_out_dim);
+  if (goal && !start) PORL_FAIL(PORL_ERR_INVALID, "null start (goal is given)");
+  if ((ep_starts == nullptr) != (ep_lengths == nullptr))
+    PORL_FAIL(PORL_ERR_INVALID, "ep_starts and ep_lengths are given together (%s is null)", ep_starts ? "ep_lengths" : "ep_starts");
+  if (ep_starts && start) PORL_FAIL(PORL_ERR_INVALID, "an episode table and start are both given: the pairs are drawn or named, not both");
+  if (ep_starts && (n_episodes < 1 || n_episodes > n_rows))
+    PORL_FAIL(PORL_ERR_INVALID, "n_episodes %lld outside [1, n_rows]", (long long)n_episodes);
+  if (!start && !ep_starts && n_rows < batch)
+    PORL_FAIL(PORL_ERR_INVALID, "n_rows %lld below batch %d: the draw takes distinct rows", (long long)n_rows, batch);
+  PairStageArgs a{};
+  a.n_rows = n_rows;
+  a.s = PairSrc{rows, (long long)row_stride, 0};
+  a.g = PairSrc{rows, (long long)row_stride, goal_col};
+  a.a = PairSrc{rows, (long long)row_stride, (int)state_part};
+  if (start) {
+    a.mode = PAIR_GIVEN;
+    a.start = reinterpret_cast<const long long*>(start); a.goal = reinterpret_cast<const long long*>(goal);
+  } else if (ep_starts) {
+    a.mode = PAIR_HINDSIGHT;
+    a.ep_starts = reinterpret_cast<const long long*>(ep_starts); a.ep_lengths = reinterpret_cast<const long long*>(ep_lengths);
+    a.E = n_episodes; a.key = ep_sm64(seed ^ ep_sm64(step));
+  } else {
+    a.mode = PAIR_PERMUTED;
+    a.seed = seed; a.step = step; a.hb = feistel_half_bits(n_rows);
+  }
+  return stage_pairs(h, a, batch, state_dim, goal_dim, act_dim, start_out, goal_out, stream);
+}
+
 // ---- the four phase calls -----------------------------------------------------------------------------------------------
 int porl_iql_value_backward(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
-  PORL_TRY(iql_enter(h, true, hp)); DevGuard _dg(h->device);
+  PORL_TRY(iql_enter(h, true, hp)); PORL_TRY(need_kind(h, false, "porl_iql_value_backward")); DevGuard _dg(h->device);
   const bool fold = (h->mode & PORL_IQL_MODE_FOLD_COMBINE) != 0;
   h->fin_v = ReduceArgs{};
   PORL_TRY(value_backward_impl(h, hp, (hipStream_t)stream, fold ? &h->fin_v : nullptr));
@@ -1016,6 +1133,7 @@ int porl_iql_policy_apply(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
 // observations.  In data-parallel mode it runs while the value-gradient all-reduce is on the wire.
 int porl_iql_policy_prefetch(porl_iql* h, void* stream) {
   PORL_TRY(check_ready(h, true));
+  PORL_TRY(need_kind(h, false, "porl_iql_policy_prefetch"));
   PORL_TRY(need_pol_target(h));
   DevGuard _dg(h->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1032,13 +1150,16 @@ int porl_iql_policy_prefetch(porl_iql* h, void* stream) {
 
 // Forward half only; a second call for the same batch does nothing.
 int porl_iql_policy_forward(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
-  PORL_TRY(iql_enter(h, true, hp)); DevGuard _dg(h->device);
+  PORL_TRY(iql_enter(h, true, hp)); PORL_TRY(need_kind(h, false, "porl_iql_policy_forward")); DevGuard _dg(h->device);
   PORL_TRY(need_pol_target(h));
   return h->pol_fwd_done ? PORL_OK : policy_forward_half(h, hp, (hipStream_t)stream);
 }
 
 int porl_iql_policy_backward(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
-  PORL_TRY(iql_enter(h, true, hp)); DevGuard _dg(h->device);
+  PORL_TRY(iql_enter(h, true, hp));
+  // on a goal-conditioned batch this call only completes porl_iql_bc_forward: the joint update's forward half needs V nets
+  if (h->pair_batch && !h->pol_fwd_done) PORL_TRY(need_kind(h, false, "porl_iql_policy_backward without porl_iql_bc_forward"));
+  DevGuard _dg(h->device);
   const bool fold = (h->mode & PORL_IQL_MODE_FOLD_COMBINE) != 0;
   h->fin_p = ReduceArgs{};
   PORL_TRY(policy_backward_impl(h, hp, (hipStream_t)stream, fold ? &h->fin_p : nullptr));
@@ -1049,7 +1170,7 @@ int porl_iql_policy_backward(porl_iql* h, const porl_iql_hyper* hp, void* stream
 // The whole update in one call.  Same arithmetic as the four phase calls; the two slab / partial-sum combines are
 // folded into the Adam launches instead of running as launches of their own.
 int porl_iql_step(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
-  PORL_TRY(iql_enter(h, true, hp)); DevGuard _dg(h->device);
+  PORL_TRY(iql_enter(h, true, hp)); PORL_TRY(need_kind(h, false, "porl_iql_step")); DevGuard _dg(h->device);
   hipStream_t s = (hipStream_t)stream;
   ReduceArgs fin{};
   PORL_TRY(value_backward_impl(h, hp, s, h->tune.iql_fold ? &fin : nullptr));
@@ -1064,7 +1185,7 @@ int porl_iql_step(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
 // mean, NLL; then the gradient half and Adam of the ordinary policy phase.  2 L + 5 launches at n_hidden = L (9 at L = 2;
 // the joint update takes 14, each plus the minibatch load).
 int porl_iql_policy_only_forward(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
-  PORL_TRY(iql_enter(h, true, hp)); DevGuard _dg(h->device);
+  PORL_TRY(iql_enter(h, true, hp)); PORL_TRY(need_kind(h, false, "porl_iql_policy_only_forward")); DevGuard _dg(h->device);
   h->pol_fwd_done = false;             // a forward half of the joint update's policy phase does not stand in for this one
   PORL_TRY(need_pol_target(h));
   return policy_only_forward_half(h, hp, (hipStream_t)stream);
@@ -1074,13 +1195,31 @@ int porl_iql_policy_only_forward(porl_iql* h, const porl_iql_hyper* hp, void* st
 // the Adam launch (single-GPU update; batch must have been loaded).  stats[1] = g_loss, stats[2] = min NLL; stats[0],
 // grads_vf, adam_*_vf, params_vf and params_tgt are not written.
 int porl_iql_policy_only_step(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
-  PORL_TRY(iql_enter(h, true, hp)); DevGuard _dg(h->device);
+  PORL_TRY(iql_enter(h, true, hp)); PORL_TRY(need_kind(h, false, "porl_iql_policy_only_step")); DevGuard _dg(h->device);
   PORL_TRY(need_pol_target(h));
   hipStream_t s = (hipStream_t)stream;
   ReduceArgs fin{};
   PORL_TRY(policy_only_forward_half(h, hp, s));
   PORL_TRY(policy_gradient_half(h, s, h->tune.iql_fold ? &fin : nullptr));
   return policy_adam(h, hp, s, &fin, "O9.");
+}
+
+// Goal-conditioned behaviour cloning (reference agent/por.py:178-183: policy(concat[obs, goal]), mean(-log_prob(actions)),
+// Adam) on a batch staged by porl_iql_load_batch_cat / porl_iql_load_batch_pairs.  L + 2 forward launches (the policy net
+// alone, mean, NLL with unit weights), the gradient half of the ordinary policy phase, Adam with the combine folded in:
+// 2 L + 4 launches at n_hidden = L (8 at L = 2), plus the load.  Group 0, the target net and stats[0] are not touched.
+int porl_iql_bc_forward(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
+  PORL_TRY(iql_enter(h, true, hp)); PORL_TRY(need_kind(h, true, "porl_iql_bc_forward")); DevGuard _dg(h->device);
+  return bc_forward_half(h, hp, (hipStream_t)stream);
+}
+
+int porl_iql_bc_step(porl_iql* h, const porl_iql_hyper* hp, void* stream) {
+  PORL_TRY(iql_enter(h, true, hp)); PORL_TRY(need_kind(h, true, "porl_iql_bc_step")); DevGuard _dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  ReduceArgs fin{};
+  PORL_TRY(bc_forward_half(h, hp, s));
+  PORL_TRY(policy_gradient_half(h, s, h->tune.iql_fold ? &fin : nullptr));
+  return policy_adam(h, hp, s, &fin, "B9.");
 }
 
 // ---- forward-only: TwinV.both, GaussianPolicy.forward / act --------------------------------------------------------------

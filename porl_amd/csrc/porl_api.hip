@@ -25,6 +25,7 @@
 #include "bcq_mask.hpp"
 #include "astar.hpp"
 #include "episodes.hpp"
+#include "pairs.hpp"
 #include "partition.hpp"
 #include "colstats.hpp"
 

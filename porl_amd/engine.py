@@ -292,6 +292,89 @@ class IqlEngine:
         self.last_batch = B
         return B
 
+    # -- goal-conditioned behaviour cloning (porl_iql_load_batch_cat / _pairs, porl_iql_bc_*) -------
+    def load_batch_cat(self, obs, goals, actions):
+        """Stage [obs | goals] as the policy's input, `actions` as its regression target and unit weights (one kernel,
+        no concatenated tensor).  obs (B, obs_dim - G), goals (B, G), actions (B, pol_out_dim): fp32 device tensors,
+        strided views with unit column stride are read in place."""
+        self._ensure_bound()
+        for t, what in ((obs, "observations"), (goals, "goals"), (actions, "actions")):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2:
+                raise RuntimeError(f"{what}: expected a 2-D tensor, got {getattr(t, 'shape', type(t))}")
+            if t.device != self.device:
+                raise RuntimeError(f"{what} on {t.device}, engine on {self.device}")
+        G = int(goals.shape[1])
+        S, A = self.cfg.obs_dim - G, self.cfg.pol_out_dim
+        if G < 1 or S < 1:
+            raise RuntimeError(f"goals: {G} columns do not fit the engine's {self.cfg.obs_dim}-wide [obs | goal] input")
+        obs, goals, actions = self._mat(obs, S, "observations"), self._mat(goals, G, "goals"), self._mat(actions, A, "actions")
+        B = obs.shape[0]
+        if goals.shape[0] != B or actions.shape[0] != B:
+            raise RuntimeError(f"observations / goals / actions batch mismatch: {B}, {goals.shape[0]}, {actions.shape[0]}")
+        if not 1 <= B <= self.cfg.max_batch:
+            raise RuntimeError(f"batch {B} outside [1, {self.cfg.max_batch}] (max_batch)")
+        # keep references alive until the staging kernel has run (stream-ordered; torch caches the memory)
+        self._held = (obs, goals, actions)
+        N.check(self._lib.porl_iql_load_batch_cat(
+            self._h, B, N.ptr(obs), obs.stride(0), N.ptr(goals), goals.stride(0), G, N.ptr(actions), actions.stride(0),
+            N.current_stream_ptr(self.device)), "porl_iql_load_batch_cat")
+        self.last_batch = B
+        return B
+
+    def _index_vec(self, t, B, what):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.device != self.device:
+            raise RuntimeError(f"{what}: expected a contiguous 1-D int64 tensor on {self.device}, got "
+                               f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
+        if t.numel() != B:
+            raise RuntimeError(f"{what}: expected {B} entries, got {t.numel()}")
+        return t
+
+    def load_batch_pairs(self, rows, batch, state_dim, act_dim, goal_col, goal_dim, start=None, goal=None, episodes=None,
+                         seed=0, step=0, start_out=None, goal_out=None):
+        """Stage `batch` (state, goal, action) samples of a packed-row store [s | r | s' | d | a] (one kernel, the store is
+        only read): s and a from row `start`, columns [goal_col, goal_col + goal_dim) from row `goal`.  `start` / `goal`
+        (int64 device tensors) name the rows (`goal` None: the start row); without `start` the rows are drawn in the
+        kernel — hindsight pairs of `episodes` (an EpisodeIndex) keyed by (seed, step) as `hindsight_indices` draws them,
+        or, without a table, distinct rows as `load_batch_sampled` draws them.  `start_out` / `goal_out` receive the rows
+        used.  A given row number outside the store stages NaN (the loss says so); nothing is read there."""
+        self._ensure_bound()
+        if rows.device != self.device or rows.dtype != torch.float32 or rows.dim() != 2 or rows.stride(1) != 1:
+            raise RuntimeError("replay rows must be a 2-D fp32 tensor on the engine's device")
+        batch = int(batch)
+        if not 1 <= batch <= self.cfg.max_batch:
+            raise RuntimeError(f"batch {batch} outside [1, {self.cfg.max_batch}] (max_batch)")
+        start, goal = self._index_vec(start, batch, "start"), self._index_vec(goal, batch, "goal")
+        start_out, goal_out = self._index_vec(start_out, batch, "start_out"), self._index_vec(goal_out, batch, "goal_out")
+        if goal is not None and start is None:
+            raise RuntimeError("goal rows are given without start rows")
+        ep_s = ep_l = None
+        n_ep = 0
+        if episodes is not None:
+            if start is not None:
+                raise RuntimeError("an episode table and start rows are both given: the pairs are drawn or named, not both")
+            if episodes.n_episodes < 1:
+                raise IndexError("load_batch_pairs: the dataset has no closed episode")
+            ep_s, ep_l, n_ep = episodes.starts, episodes.lengths, episodes.n_episodes
+            for t, what in ((ep_s, "episode starts"), (ep_l, "episode lengths")):
+                self._index_vec(t, n_ep, what)
+        n = rows.shape[0]
+        stride = rows.stride(0) if n > 1 else max(rows.stride(0), rows.shape[1])
+        mask = 0xFFFFFFFFFFFFFFFF
+        self._held = (start, goal, ep_s, ep_l)
+        N.check(self._lib.porl_iql_load_batch_pairs(
+            self._h, batch, N.ptr(rows), stride, n, int(state_dim), int(act_dim), int(goal_col), int(goal_dim),
+            N.ptr(start), N.ptr(goal), N.ptr(ep_s), N.ptr(ep_l), n_ep, seed & mask, step & mask, N.ptr(start_out),
+            N.ptr(goal_out), N.current_stream_ptr(self.device)), "porl_iql_load_batch_pairs")
+        self.last_batch = batch
+        return batch
+
+    # the behaviour-cloning step on a batch staged by the two loaders above: the whole step, or its forward half followed by
+    # policy_backward (/ policy_apply)
+    def bc_step(self, hp): self._phase("porl_iql_bc_step", hp)
+    def bc_forward(self, hp): self._phase("porl_iql_bc_forward", hp)
+
     def set_stats(self, stats):
         """Point the loss statistics of the following updates at `stats` (>= 8 fp32 on the device)."""
         self._ensure_bound()
