@@ -946,6 +946,83 @@ int porl_per_sample_slots(const double* tree, int64_t capacity, const double* u,
 int porl_per_update_f32(double* tree, int64_t capacity, const int64_t* tree_idx, const float* td_abs, int32_t n,
                         double eps, double alpha, int32_t* stamp, void* stream);
 
+/* The lidar navigation task on the device (env/gazebo.py without ROS and Gazebo; csrc/navsim.hpp): a unicycle step and
+ * a 2-D ray cast against a world of wall segments and pillars replace the physics and the laser.  One workgroup per
+ * robot, one launch per call for any n, no host synchronisation.
+ *
+ * World: segments (M, 4) fp32 x1 y1 x2 y2 and circles (C, 3) fp32 cx cy r, dense, on the device, shared by all robots;
+ * M + C <= PORL_NAV_MAX_PRIMS.  Coordinates are widened to fp64 exactly; all geometry is fp64 and a range is rounded once
+ * to fp32.  A circle is solid and seen from outside (near root only).  beam_dirs (n_beams, 2) fp64: cos, sin of beam i's
+ * angle in the robot frame, built by the caller (i * pi / 180 for 360 beams) and rotated by sincos(yaw) in the kernel.
+ * A beam's range is the smallest t with 0 < t < range_max over segments (den != 0, 0 <= s <= 1) and circles (disc >= 0,
+ * t = b - sqrt(disc)), else no_return.
+ *
+ * Per robot: state (n, 8) fp64 x y yaw goal_x goal_y prev_goal_distance prev_goal_angle 0; counters (n, 4) int64 n_step
+ * episode status draws_used.  Status: PORL_NAV_RUNNING / HIT / GOAL / TIMELIMITED, and bit PORL_NAV_DRAW_CAP when a reset
+ * stopped at PORL_NAV_MAX_DRAWS draws.  Observation rows (S wide): layout PORL_NAV_LAYOUT_GOAL [scan | goal in the robot
+ * frame], S = n_beams + 2 (getState, env/gazebo.py:135-147); PORL_NAV_LAYOUT_POSE [scan | x y | yaw | goal_x goal_y],
+ * S = n_beams + 5 (the rows preprocess.py:23-36 reads). */
+#define PORL_NAV_MAX_PRIMS 2048
+#define PORL_NAV_MAX_BEAMS 1024
+#define PORL_NAV_MAX_DRAWS 256
+#define PORL_NAV_RUNNING 0
+#define PORL_NAV_HIT 1
+#define PORL_NAV_GOAL 2
+#define PORL_NAV_TIMELIMITED 3   /* truncated without termination */
+#define PORL_NAV_DRAW_CAP 256    /* status bit 8 */
+#define PORL_NAV_LAYOUT_GOAL 0
+#define PORL_NAV_LAYOUT_POSE 1
+#define PORL_NAV_TERMINATED 1    /* flags bit 0 */
+#define PORL_NAV_TRUNCATED 2     /* flags bit 1 */
+typedef struct porl_nav_params {
+  double dt;            /* 0.2   seconds per step (the scan period env.step waits for) */
+  double max_lin_vel;   /* 0.15  v = clamp(a0, 0, max_lin_vel) */
+  double max_ang_vel;   /* 1.5   w = clamp(a1, -max_ang_vel, max_ang_vel) */
+  double min_range;     /* 0.13  0 < min(scan) < min_range: hit; max_lin_vel * dt < min_range is required */
+  double range_max;     /* 3.5 */
+  double no_return;     /* 10.0  what lidarPreprocess makes of inf */
+  double goal_radius;   /* 0.2 */
+  double hit_reward;    /* -500 */
+  double goal_reward;   /* +500 */
+  double origin_x;      /* random_pts_map: map_x + (rank % 4) * 5 */
+  double origin_y;      /*                 map_y + (3 - rank / 4) * 5 */
+  double spawn_lo;      /* 0.16  a coordinate is floor(cells * u) + spawn_lo + spawn_span * u' */
+  double spawn_span;    /* 0.68 */
+  double min_gap_sq;    /* 0.01  redraw while (x1 - x2)^2 < min_gap_sq, the same on y */
+  double goal_dist_lo;  /* 0.3   redraw the goal while dist < goal_dist_lo or dist > goal_dist_hi */
+  double goal_dist_hi;  /* 3.5 */
+  int32_t n_beams;      /* 360   1 .. PORL_NAV_MAX_BEAMS */
+  int32_t episode_step; /* 500   truncated = n_step >= episode_step */
+  int32_t cells;        /* 5     randint(cells) */
+  int32_t layout;       /* PORL_NAV_LAYOUT_* */
+  int32_t auto_reset;   /* != 0: a robot that finishes in porl_nav_step is reset in the same launch */
+  int32_t reserved;     /* 0 */
+} porl_nav_params;
+/* The ray cast alone: out[i * out_stride + b] = range of beam b from poses[i] = (x, y, yaw), fp64 (n, 3). */
+int porl_nav_scan(const float* segments, int32_t M, const float* circles, int32_t C, const double* poses,
+                  const double* beam_dirs, const porl_nav_params* params, float* out, int64_t out_stride, int64_t n,
+                  void* stream);
+/* random_pts_map (env/gazebo.py:280-318) statement for statement on a counter stream: key = sm64(seed ^ sm64(env_offset +
+ * i)), draw j of episode e is u = (sm64(key ^ sm64(256 e + j)) >> 11) * 2^-53 (sm64 = the splitmix64 finaliser of
+ * porl_hindsight_pairs); each coordinate takes an integer draw, then a uniform draw.  Robot i with mask == NULL or
+ * mask[i] != 0: episode += 1, new start and goal, yaw = 0, n_step = 0, prev_* from the new pose, status running,
+ * obs[i] = the observation from there.  Other robots are not touched.  A spawn is NOT tested against the world. */
+int porl_nav_reset(const float* segments, int32_t M, const float* circles, int32_t C, const double* beam_dirs,
+                   const porl_nav_params* params, uint64_t seed, int64_t env_offset, const uint8_t* mask, double* state,
+                   int64_t* counters, float* obs, int64_t obs_stride, int64_t n, void* stream);
+/* One step of every running robot (env.step, env/gazebo.py:149-181, getSarsa :91-133): clip the command actions[i] =
+ * (v, w) (a non-finite component counts as 0), exact arc over dt, scan at the new pose, relative goal, shaped reward,
+ * hit (reward hit_reward) then goal (goal_reward, wins), n_step += 1, truncated = n_step >= episode_step.
+ * obs (n, S) in/out: the observation each robot acted on; on return the one to act on next (next_obs, or with auto_reset
+ * the observation after the reset).  next_obs, reward (n), flags (n) int32, status (n) int32 are required.  rows is
+ * optional: robot i's transition [s | r | s' | terminated | v w] (2S + 4 floats, the clipped command) at rows + i *
+ * row_stride.  A robot whose status is not running is left as it is: reward 0, flags 0, its row all NaN. */
+int porl_nav_step(const float* segments, int32_t M, const float* circles, int32_t C, const double* beam_dirs,
+                  const porl_nav_params* params, uint64_t seed, int64_t env_offset, const float* actions,
+                  int64_t act_stride, double* state, int64_t* counters, float* obs, int64_t obs_stride, float* next_obs,
+                  int64_t next_stride, float* reward, int32_t* flags, int32_t* status, float* rows, int64_t row_stride,
+                  int64_t n, void* stream);
+
 /* Experiment knobs (scheduling only, never the mathematics).  "gemm_lds_pad": extra dynamic LDS bytes per GEMM block,
  * limiting how many blocks share a CU.  "qnet_fused": 0 forces the multi-launch CQL path.  porl_tune_set sets the process
  * defaults, copied by porl_iql / qnet / enc handles when created; porl_iql_tune_set sets one live IQL engine's copy. */

@@ -43,6 +43,7 @@ SYMBOLS = [
     "porl_gather_pairs",
     "porl_partition_workspace", "porl_partition_mask", "porl_partition_rows",
     "porl_colstats_workspace", "porl_col_stats", "porl_affine_cols",
+    "porl_nav_scan", "porl_nav_reset", "porl_nav_step",
 ]
 
 
@@ -145,6 +146,13 @@ class PartitionBox(C.Structure):
 
 class ColSpan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("col0", "n_cols", "param0", "flags")]      # flags bit 0: multiply
+
+
+class NavParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("dt", "max_lin_vel", "max_ang_vel", "min_range", "range_max", "no_return",
+                                          "goal_radius", "hit_reward", "goal_reward", "origin_x", "origin_y", "spawn_lo",
+                                          "spawn_span", "min_gap_sq", "goal_dist_lo", "goal_dist_hi")] + \
+               [(n, C.c_int32) for n in ("n_beams", "episode_step", "cells", "layout", "auto_reset", "reserved")]
 
 
 class ProfEntry(C.Structure):
@@ -307,6 +315,10 @@ def _declare(lib):
     lib.porl_colstats_workspace.restype = i64
     lib.porl_col_stats.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp]
     lib.porl_affine_cols.argtypes = [vp, i64, i64, i32, C.POINTER(ColSpan), i32, vp, vp, vp, i32, vp, i64, vp]
+    lib.porl_nav_scan.argtypes = [vp, i32, vp, i32, vp, vp, C.POINTER(NavParams), vp, i64, i64, vp]
+    lib.porl_nav_reset.argtypes = [vp, i32, vp, i32, vp, C.POINTER(NavParams), C.c_uint64, i64, vp, vp, vp, vp, i64, i64, vp]
+    lib.porl_nav_step.argtypes = [vp, i32, vp, i32, vp, C.POINTER(NavParams), C.c_uint64, i64, vp, i64, vp, vp, vp, i64, vp,
+                                  i64, vp, vp, vp, vp, i64, i64, vp]
     lib.porl_prof_enable.argtypes = [C.c_int]
     lib.porl_prof_read.argtypes = [C.POINTER(ProfEntry), C.c_int]
     for name in SYMBOLS:

@@ -28,6 +28,7 @@
 #include "pairs.hpp"
 #include "partition.hpp"
 #include "colstats.hpp"
+#include "navsim.hpp"
 
 using namespace porl;
 
@@ -870,3 +871,4 @@ int porl_prof_read(porl_prof_entry* out, int max_entries) {
 #include "episodes_api.inc"
 #include "partition_api.inc"
 #include "colstats_api.inc"
+#include "navsim_api.inc"

@@ -5,7 +5,7 @@ The operators are a thin layer: tensors in, raw pointers + sizes + the current H
 handed to libporl_hip.so.  Engines (which own flat parameter groups, Adam state and workspace) are referred to by an
 integer handle obtained from `register_engine(obj)`; `por_step` / `iql_value_step` / `awr_policy_step` / `cql_step`
 are what the agent classes run per minibatch, `replay_gather` / `adam_ema_sweep` / `mlp_forward` / `gemm_f32` /
-`sample_indices` / `state2costmap` / `astar_label` are the building blocks.
+`sample_indices` / `state2costmap` / `astar_label` / `nav_scan` are the building blocks.
 
 Only the CUDA (= HIP on ROCm) dispatch key has an implementation.  There is NO CPU kernel: calling an operator with
 CPU tensors raises `NativeError`, like every other entry of this package.
@@ -71,6 +71,9 @@ SCHEMAS = {
     "col_stats": "(Tensor rows, int col0, int n_cols) -> Tensor",
     # rows[:, c0+j] = fl(fl(rows[:, c0+j] - shift[p0+j]) / div[p0+j]) [* mul[p0+j]] in place; spans = (c0, n_cols, p0, flags)*
     "affine_cols": "(Tensor(a!) rows, int[] spans, Tensor shift, Tensor div, Tensor? mul) -> ()",
+    # lidar ranges (n, n_beams) fp32 from poses (n, 3) fp64 `x y yaw` in a world of segments (M, 4) and circles (C, 3)
+    "nav_scan": "(Tensor segments, Tensor circles, Tensor poses, int n_beams=360, float range_max=3.5, "
+                "float no_return=10.) -> Tensor",
 }
 for _name, _schema in SCHEMAS.items():
     LIB.define(_name + _schema)
@@ -190,10 +193,15 @@ def _affine_cols(rows, spans, shift, div, mul):
     affine_cols_device(_as_rows(rows), [tuple(spans[i:i + 4]) for i in range(0, len(spans), 4)], shift, div, mul)
 
 
+def _nav_scan(segments, circles, poses, n_beams=360, range_max=3.5, no_return=10.):
+    from .env.navsim import nav_scan
+    return nav_scan(segments, circles, poses, n_beams=n_beams, range_max=range_max, no_return=no_return)
+
+
 _IMPLS = dict(por_step=_por_step, iql_value_step=_iql_value_step, awr_policy_step=_awr_policy_step, cql_step=_cql_step,
               replay_gather=_replay_gather, adam_ema_sweep=_adam_ema_sweep, mlp_forward=_mlp_forward, gemm_f32=_gemm_f32,
               sample_indices=_sample_indices, state2costmap=_state2costmap, astar_label=_astar_label,
-              col_stats=_col_stats, affine_cols=_affine_cols)
+              col_stats=_col_stats, affine_cols=_affine_cols, nav_scan=_nav_scan)
 
 
 def _no_cpu(name):
