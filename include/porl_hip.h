@@ -1023,6 +1023,57 @@ int porl_nav_step(const float* segments, int32_t M, const float* circles, int32_
                   int64_t next_stride, float* reward, int32_t* flags, int32_t* status, float* rows, int64_t row_stride,
                   int64_t n, void* stream);
 
+/* The discrete lidar navigation task (env/env.py, the 5-action task runner.py hands to DQN_CQL; csrc/navsim_discrete.hpp)
+ * on the same world, ray cast, reset draw and counter stream as above.  The robot drives at lin_vel; action a of
+ * n_actions picks w = ((n_actions - 1) / 2 - a) * ang_step (an index outside [0, n_actions) is clamped into range).
+ * Observation rows [scan | heading | distance], S = n_beams + 2 (params->layout must be PORL_NAV_LAYOUT_GOAL), heading =
+ * round2(wrap(atan2(gy - y, gx - x) - yaw)), distance = round2(|goal - position|), round2(x) = rint(100 x) / 100 in fp64.
+ * Hit: 0 < min(scan) < min_range; goal: distance < goal_radius, and the goal wins.  Reward: round2(5 tr) * 2^(distance /
+ * goal_distance), tr = 1 - 4 |0.5 - frac(0.25 + ((0.5 angle) mod 2 pi) / pi)|, angle = -pi/4 + heading + pi/8 a + pi/2
+ * (mod non-negative), or goal_reward / hit_reward of this struct (params' two are not read).  truncated = n_step >=
+ * episode_step; the status is PORL_NAV_TIMELIMITED then, also on a step that terminated (flags keep both bits), and the
+ * reward is not altered.  state (n, 8) fp64: x y yaw goal_x goal_y 0 0 goal_distance (the rounded distance at reset);
+ * counters as above.  Geometry, limits and reset constants travel in porl_nav_params (the reference's reset uses
+ * goal_dist_lo = 0.25 and maps a beam without return to no_return = 3.5). */
+typedef struct porl_nav_discrete {
+  int32_t n_actions;    /* 5     1 .. 5: the reference's yaw table has five entries */
+  double lin_vel;       /* 0.15  lin_vel * dt < min_range is required */
+  double ang_step;      /* 0.75  max_ang_vel * 0.5 */
+  double goal_reward;   /* +200 */
+  double hit_reward;    /* -200 */
+} porl_nav_discrete;
+/* porl_nav_reset for the discrete task; returns (n) fp64, optional: the running episode return, zeroed for a robot that
+ * is reset. */
+int porl_nav_dreset(const float* segments, int32_t M, const float* circles, int32_t C, const double* beam_dirs,
+                    const porl_nav_params* params, const porl_nav_discrete* task, uint64_t seed, int64_t env_offset,
+                    const uint8_t* mask, double* state, int64_t* counters, float* obs, int64_t obs_stride, double* returns,
+                    int64_t n, void* stream);
+/* One step of every running robot with actions (n) int64.  obs, next_obs, reward, flags, status as porl_nav_step; a robot
+ * whose status is not running is left as it is (reward 0, flags 0) and writes to neither optional output:
+ *   replay (NULL: none): robot i's transition goes into slot (replay_base + i) % capacity of the five arrays — states the
+ *     observation acted on, next_states the one reached, actions the clamped index, rewards, dones = terminated |
+ *     truncated as 1.0 / 0.0 (what dqn_trainer.py:119-180 pushes).  Rows are S floats, dense.  n <= capacity and
+ *     0 <= replay_base < capacity are required: no two robots share a slot.
+ *   tallies (n, 4) fp64 with returns (n) fp64 (both or neither): returns[i] += reward; at an episode's end tallies[i] +=
+ *     (1, returns[i], goal, hit) and returns[i] = 0.
+ * No atomics, no communication between blocks.  Every argument is checked before the launch (PORL_ERR_INVALID). */
+int porl_nav_dstep(const float* segments, int32_t M, const float* circles, int32_t C, const double* beam_dirs,
+                   const porl_nav_params* params, const porl_nav_discrete* task, uint64_t seed, int64_t env_offset,
+                   const int64_t* actions, double* state, int64_t* counters, float* obs, int64_t obs_stride, float* next_obs,
+                   int64_t next_stride, float* reward, int32_t* flags, int32_t* status, const porl_qnet_mirror* replay,
+                   int64_t replay_base, double* tallies, double* returns, int64_t n, void* stream);
+/* Epsilon-greedy over a table q (n, n_actions) fp32 with row stride q_rs, n_actions <= 64, into out (n) int64 on the
+ * device; nothing is read back.  Robot i at act-step t draws u1, u2 = draws 0, 1 of "episode" t of the stream keyed
+ * sm64(seed ^ sm64(env_offset + i)) (porl_nav_reset's construction); u1 < epsilon: floor(n_actions * u2); otherwise the
+ * arg-max, ties to the lowest index, a NaN counting as the maximum (torch.argmax). */
+int porl_qnet_select(const float* q, int64_t q_rs, int32_t n_actions, int64_t n, double epsilon, uint64_t seed,
+                     int64_t env_offset, uint64_t t, int64_t* out, void* stream);
+/* porl_qnet_forward on n rows of states, walked in chunks of the engine's max_batch, into the caller's scratch q (n,
+ * n_actions), then porl_qnet_select on it: acting for n robots from one call.  Plain-Q networks only (DQN, Double DQN,
+ * Dueling through the composed output layer, CQL); C51, QR-DQN and IQN are out of scope. */
+int porl_qnet_act_rows(porl_qnet* h, int which, const float* states, int64_t s_rs, int64_t n, float* q, int64_t q_rs,
+                       double epsilon, uint64_t seed, int64_t env_offset, uint64_t t, int64_t* out, void* stream);
+
 /* Experiment knobs (scheduling only, never the mathematics).  "gemm_lds_pad": extra dynamic LDS bytes per GEMM block,
  * limiting how many blocks share a CU.  "qnet_fused": 0 forces the multi-launch CQL path.  porl_tune_set sets the process
  * defaults, copied by porl_iql / qnet / enc handles when created; porl_iql_tune_set sets one live IQL engine's copy. */

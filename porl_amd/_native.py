@@ -44,6 +44,7 @@ SYMBOLS = [
     "porl_partition_workspace", "porl_partition_mask", "porl_partition_rows",
     "porl_colstats_workspace", "porl_col_stats", "porl_affine_cols",
     "porl_nav_scan", "porl_nav_reset", "porl_nav_step",
+    "porl_nav_dreset", "porl_nav_dstep", "porl_qnet_select", "porl_qnet_act_rows",
 ]
 
 
@@ -153,6 +154,11 @@ class NavParams(C.Structure):
                                           "goal_radius", "hit_reward", "goal_reward", "origin_x", "origin_y", "spawn_lo",
                                           "spawn_span", "min_gap_sq", "goal_dist_lo", "goal_dist_hi")] + \
                [(n, C.c_int32) for n in ("n_beams", "episode_step", "cells", "layout", "auto_reset", "reserved")]
+
+
+class NavDiscrete(C.Structure):
+    _fields_ = [("n_actions", C.c_int32), ("lin_vel", C.c_double), ("ang_step", C.c_double), ("goal_reward", C.c_double),
+                ("hit_reward", C.c_double)]
 
 
 class ProfEntry(C.Structure):
@@ -319,6 +325,12 @@ def _declare(lib):
     lib.porl_nav_reset.argtypes = [vp, i32, vp, i32, vp, C.POINTER(NavParams), C.c_uint64, i64, vp, vp, vp, vp, i64, i64, vp]
     lib.porl_nav_step.argtypes = [vp, i32, vp, i32, vp, C.POINTER(NavParams), C.c_uint64, i64, vp, i64, vp, vp, vp, i64, vp,
                                   i64, vp, vp, vp, vp, i64, i64, vp]
+    lib.porl_nav_dreset.argtypes = [vp, i32, vp, i32, vp, C.POINTER(NavParams), C.POINTER(NavDiscrete), C.c_uint64, i64, vp,
+                                    vp, vp, vp, i64, vp, i64, vp]
+    lib.porl_nav_dstep.argtypes = [vp, i32, vp, i32, vp, C.POINTER(NavParams), C.POINTER(NavDiscrete), C.c_uint64, i64, vp,
+                                   vp, vp, vp, i64, vp, i64, vp, vp, vp, C.POINTER(QnetMirror), i64, vp, vp, i64, vp]
+    lib.porl_qnet_select.argtypes = [vp, i64, i32, i64, f64, C.c_uint64, i64, C.c_uint64, vp, vp]
+    lib.porl_qnet_act_rows.argtypes = [vp, C.c_int, vp, i64, i64, vp, i64, f64, C.c_uint64, i64, C.c_uint64, vp, vp]
     lib.porl_prof_enable.argtypes = [C.c_int]
     lib.porl_prof_read.argtypes = [C.POINTER(ProfEntry), C.c_int]
     for name in SYMBOLS:

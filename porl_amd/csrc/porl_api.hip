@@ -29,6 +29,7 @@
 #include "partition.hpp"
 #include "colstats.hpp"
 #include "navsim.hpp"
+#include "navsim_discrete.hpp"
 
 using namespace porl;
 
@@ -872,3 +873,4 @@ int porl_prof_read(porl_prof_entry* out, int max_entries) {
 #include "partition_api.inc"
 #include "colstats_api.inc"
 #include "navsim_api.inc"
+#include "navsim_discrete_api.inc"

@@ -791,6 +791,22 @@ class QnetEngine:
                                         N.current_stream_ptr(self.device)), "porl_qnet_act")
         return out
 
+    def act_rows(self, states, epsilon, seed, t, env_offset=0, q=None, out=None, which=0):
+        """Epsilon-greedy actions (n,) int64 for n rows of states from one native call (porl_qnet_act_rows): the batched
+        forward in chunks of max_batch into the scratch `q` (n, A), then qnet_select's kernel.  Plain-Q networks only."""
+        self._ensure_bound()
+        x = self._states(states)
+        if q is None:
+            q = torch.empty(x.shape[0], self.cfg.n_actions, dtype=torch.float32, device=self.device)
+        if q.shape != (x.shape[0], self.cfg.n_actions) or q.device != self.device:
+            raise RuntimeError(f"q: expected ({x.shape[0]}, {self.cfg.n_actions}) on {self.device}, got {tuple(q.shape)} on {q.device}")
+        out, q_rs = _select_args(q, out)
+        N.check(self._lib.porl_qnet_act_rows(self._h, int(which), N.ptr(x), x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1]),
+                                             x.shape[0], N.ptr(q), q_rs, float(epsilon), int(seed) & (2 ** 64 - 1),
+                                             int(env_offset), int(t), N.ptr(out), N.current_stream_ptr(self.device)),
+                "porl_qnet_act_rows")
+        return out
+
     def penalty(self, states, actions):
         self._ensure_bound()
         states = self._states(states)
@@ -951,6 +967,26 @@ def sample_indices(n_rows, batch, seed, step, out=None, base=0, device="cuda"):
         out = torch.empty(batch, dtype=torch.int64, device=device)
     N.check(N.lib().porl_sample_indices(n_rows, batch, seed, step, base, N.ptr(out), N.current_stream_ptr(out)),
             "porl_sample_indices")
+    return out
+
+
+def _select_args(q, out):
+    if q.dim() != 2 or q.dtype != torch.float32 or q.device.type != "cuda" or (q.shape[1] > 1 and q.stride(1) != 1):
+        raise RuntimeError("q: need a (n, n_actions) float32 table with unit column stride on a HIP device")
+    n = q.shape[0]
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=q.device)
+    elif out.dtype != torch.int64 or out.device != q.device or out.shape != (n,) or not out.is_contiguous():
+        raise RuntimeError(f"out: need a contiguous ({n},) int64 tensor on {q.device}")
+    return out, (q.stride(0) if n > 1 else max(q.stride(0), q.shape[1]))
+
+
+def qnet_select(q, epsilon, seed, t, env_offset=0, out=None):
+    """Epsilon-greedy actions (n,) int64 on the device from action values q (n, A <= 64) (porl_qnet_select): robot i at
+    act-step `t` draws from the counter stream keyed (seed, env_offset + i, t); nothing is read back."""
+    out, q_rs = _select_args(q, out)
+    N.check(N.lib().porl_qnet_select(N.ptr(q), q_rs, q.shape[1], q.shape[0], float(epsilon), int(seed) & (2 ** 64 - 1),
+                                     int(env_offset), int(t), N.ptr(out), N.current_stream_ptr(q)), "porl_qnet_select")
     return out
 
 

@@ -300,6 +300,12 @@ class CQLTrainer:
         return online.run(self, env, policy, num_episodes, max_steps, self.training_learning_step, self.replay_buffer,
                           self.replay_buffer.push, fast)
 
+    def train_vectorized(self, sim, n_steps, **kw):
+        """act -> step -> learn with the N robots of a DiscreteLidarNavSim and no host synchronisation inside the loop
+        (train/vector_online.py).  PER and BCQ trainers raise NotImplementedError: they run through train_online(Env(...))."""
+        from .vector_online import train_vectorized
+        return train_vectorized(self, sim, n_steps, **kw)
+
     # -- acting -----------------------------------------------------------------------------------
     def get_action(self, state: np.ndarray) -> int:
         x = torch.as_tensor(np.asarray(state), dtype=torch.float32, device=self.device).unsqueeze(0)

@@ -1,0 +1,190 @@
+"""`train_vectorized` (porl_amd/train/vector_online.py): act -> step -> learn with 64 robots of the discrete lidar task and
+no host synchronisation inside the loop.  Lattice world, n_beams = 36 (S = 38), hidden [64, 64], batch 32, 48 steps in
+blocks of 16, learning from 128 rows on: the first learn step follows the second simulator step, so 47 learn steps.
+
+Everything asserted is an identity (bit-equal reruns, bit-equal hand-written loop, counts) or finiteness: no tolerance."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+N_ENVS, N_BEAMS, S, A, B, STEPS, BLOCK, STARTS, SEED = 64, 36, 38, 5, 32, 48, 16, 128, 5
+
+
+def make_trainer(kind, tmp_path):
+    from porl_amd.net.q_network import DuelingQNetwork, QNetwork
+    from porl_amd.train.cql_trainer import CQLTrainer
+    from porl_amd.train.dddqn_trainer import DDDQNTrainer
+    from porl_amd.train.dqn_trainer import DDQNTrainer, DQNTrainer
+    torch.manual_seed(0)
+    kw = dict(epsilon=1.0, epsilon_min=0.05, epsilon_decay=0.5, update_target_freq=2, device=DEV, batch_size=B,
+              log_dir=str(tmp_path))
+    net = lambda s, a: QNetwork(s, a, [64, 64])
+    if kind == "dqn":
+        return DQNTrainer(S, A, 0.99, network=net, **kw)
+    if kind == "dqn_wide":                                      # not on the one-launch step kernel: sample_indices, gather, learn_on
+        return DQNTrainer(S, A, 0.99, network=lambda s, a: QNetwork(s, a, [256, 256]), **kw)
+    if kind == "ddqn":
+        return DDQNTrainer(S, A, 0.99, network=net, **kw)
+    if kind == "dueling":
+        return DDDQNTrainer(S, A, 0.99, network=lambda s, a: DuelingQNetwork(s, a, [64, 64]), **kw)
+    return CQLTrainer(S, A, 0.99, network=net, alpha=1, **kw)
+
+
+def make_sim():
+    from porl_amd.env import DiscreteLidarNavSim, NavWorld
+    return DiscreteLidarNavSim(NavWorld.lattice(), N_ENVS, n_actions=A, seed=3, auto_reset=True, n_beams=N_BEAMS, episode_step=20)
+
+
+def run(kind, tmp_path, n_steps=STEPS):
+    from porl_amd.buffer.device_replay import DeviceReplay
+    t, sim = make_trainer(kind, tmp_path), make_sim()
+    replay = DeviceReplay(2000, S, DEV)                         # 64 * 48 = 3072 rows: the ring wraps
+    out = t.train_vectorized(sim, n_steps, replay=replay, learn_per_step=1, learning_starts=STARTS, block=BLOCK, seed=SEED)
+    return t, sim, replay, out
+
+
+def snapshot(t, sim, replay):
+    eng = t._engine
+    xs = [eng.params, eng.params_tgt, eng.adam_m, eng.adam_v, sim.state, sim.counters, sim.obs, sim.tallies, *replay.arrays()]
+    if t._dueling is not None:
+        xs += [t._dueling.flat, t._dueling.flat_tgt, t._dueling.m, t._dueling.v]
+    return [x.clone() for x in xs]
+
+
+def assert_same(a, b):
+    assert len(a) == len(b)
+    for k, (x, y) in enumerate(zip(a, b)):
+        assert torch.equal(x, y) or (torch.equal(torch.isnan(x), torch.isnan(y)) and torch.equal(torch.nan_to_num(x), torch.nan_to_num(y))), k
+
+
+def hand_written(kind, tmp_path):
+    """The same native calls, written out: act_rows -> step -> learn, the block schedule on the host."""
+    from porl_amd import engine as E
+    from porl_amd.buffer.device_replay import DeviceReplay
+    t, sim = make_trainer(kind, tmp_path), make_sim()
+    eng = t._engine
+    replay = DeviceReplay(2000, S, DEV)
+    sim.reset()
+    q = torch.empty(N_ENVS, A, device=DEV)
+    acts = torch.empty(N_ENVS, dtype=torch.int64, device=DEV)
+    losses, draw, eps = [], 0, 1.0
+    for it in range(STEPS):
+        eng.act_rows(sim.obs, eps, SEED, it, env_offset=0, q=q, out=acts)
+        sim.step(acts, replay=replay)
+        if len(replay) >= STARTS:
+            hp = t.optimizer.hyper(t.gamma, float(t.alpha), 1.0 / B)
+            if eng.can_sample:
+                eng.learn_sampled(hp, *replay.arrays(), len(replay), B, SEED, draw, variant=t._rows_variant())
+            else:
+                idx = E.sample_indices(len(replay), B, SEED, draw, device=eng.device)
+                eng.learn_indexed(hp, *replay.arrays(), idx, variant=t._rows_variant())
+            t.optimizer.step_count = hp.step
+            draw += 1
+            losses.append(eng.stats[:1].clone())
+        if (it + 1) % BLOCK == 0:
+            eps = max(0.05, eps * 0.5)
+            if ((it + 1) // BLOCK - 1) % 2 == 0:
+                t.sync_target()
+    return t, sim, replay, torch.cat(losses).cpu().numpy()
+
+
+def test_dqn_vectorized_training(tmp_path):
+    t, sim, replay, out = run("dqn", tmp_path)
+    eng = t._engine
+    assert eng.fused                                            # [64, 64] at S = 38 runs on the one-launch step kernel
+    assert out["transitions"] == N_ENVS * STEPS == 3072
+    assert out["learn_steps"] == STEPS - 1 == t.optimizer.step_count == len(out["losses"])
+    assert bool(torch.isfinite(torch.from_numpy(out["losses"])).all()) and (out["losses"] > 0).any()
+    assert len(replay) == 2000 and replay.position == 3072 % 2000
+    assert t.epsilon == 0.125                                   # three blocks of decay 0.5
+    # the tallies are the simulator's table summed over robots: episodes of at most 20 steps over 48 steps
+    tal = sim.tallies.sum(0).cpu().numpy()
+    assert (out["tallies"] == tal).all() and 2 * N_ENVS <= tal[0] and tal[2] + tal[3] <= tal[0]
+    # the parameters moved; the target network was synchronised after block 2 (b = 2, update_target_freq = 2)
+    fresh = make_trainer("dqn", tmp_path)
+    assert not torch.equal(fresh._engine.params, eng.params)
+    assert torch.equal(eng.params, eng.params_tgt)
+    # two runs from the same seeds: bit-identical parameters, replay arrays and loss logs
+    t2, sim2, replay2, out2 = run("dqn", tmp_path)
+    assert_same(snapshot(t, sim, replay), snapshot(t2, sim2, replay2))
+    assert (out["losses"] == out2["losses"]).all() and (out["tallies"] == out2["tallies"]).all()
+    # a hand-written loop of the same native calls reproduces them bit for bit
+    t3, sim3, replay3, losses3 = hand_written("dqn", tmp_path)
+    assert_same(snapshot(t, sim, replay), snapshot(t3, sim3, replay3))
+    assert (out["losses"] == losses3).all()
+    # the target equals the online network exactly where a sync is due (after blocks 0 and 2) and differs in between
+    ta, *_ = run("dqn", tmp_path, n_steps=BLOCK)
+    assert torch.equal(ta._engine.params, ta._engine.params_tgt) and ta.epsilon == 0.5
+    assert not torch.equal(ta._engine.params, fresh._engine.params)
+    tb, *_ = run("dqn", tmp_path, n_steps=2 * BLOCK)
+    assert not torch.equal(tb._engine.params, tb._engine.params_tgt) and tb.epsilon == 0.25
+    # a second call continues the first: 16 + 32 steps are the 48-step run
+    sim_c = make_sim()
+    from porl_amd.buffer.device_replay import DeviceReplay
+    tc, replay_c = make_trainer("dqn", tmp_path), DeviceReplay(2000, S, DEV)
+    kw = dict(replay=replay_c, learning_starts=STARTS, block=BLOCK, seed=SEED)
+    first = tc.train_vectorized(sim_c, BLOCK, **kw)
+    second = tc.train_vectorized(sim_c, 2 * BLOCK, **kw)
+    assert_same(snapshot(t, sim, replay), snapshot(tc, sim_c, replay_c))
+    assert first["learn_steps"] + second["learn_steps"] == STEPS - 1
+
+
+@pytest.mark.parametrize("kind", ["ddqn", "cql", "dueling", "dqn_wide"])
+def test_other_plain_q_trainers_are_deterministic_and_finite(kind, tmp_path):
+    t, sim, replay, out = run(kind, tmp_path)
+    assert t._engine.fused == (kind != "dqn_wide")
+    t2, sim2, replay2, out2 = run(kind, tmp_path)
+    assert out["learn_steps"] == STEPS - 1 == t.optimizer.step_count
+    assert bool(torch.isfinite(torch.from_numpy(out["losses"])).all())
+    assert_same(snapshot(t, sim, replay), snapshot(t2, sim2, replay2))
+    assert (out["losses"] == out2["losses"]).all()
+    assert bool(torch.isfinite(t._engine.params).all())
+    assert not torch.equal(make_trainer(kind, tmp_path)._engine.params, t._engine.params)
+
+
+def test_the_reference_width_learns_through_learn_on(tmp_path):
+    """S = 362, the reference's observation, is wider than the one-launch step kernel takes, so a learn step is
+    sample_indices, a gather and the trainer's learn_on (Double DQN's).  16 robots, 12 steps, learning from 64 rows on."""
+    from porl_amd.buffer.device_replay import DeviceReplay
+    from porl_amd.env import DiscreteLidarNavSim, NavWorld
+    from porl_amd.net.q_network import QNetwork
+    from porl_amd.train.dqn_trainer import DDQNTrainer
+
+    def once():
+        torch.manual_seed(0)
+        t = DDQNTrainer(362, A, 0.99, device=DEV, batch_size=B, log_dir=str(tmp_path), network=lambda s, a: QNetwork(s, a, [64, 64]))
+        sim = DiscreteLidarNavSim(NavWorld.lattice(), 16, seed=3, auto_reset=True, episode_step=5)
+        replay = DeviceReplay(100, 362, DEV)
+        out = t.train_vectorized(sim, 12, replay=replay, learning_starts=64, block=4, seed=SEED)
+        return t, sim, replay, out
+    t, sim, replay, out = once()
+    assert not t._engine.fused and not t._engine.can_sample
+    assert out["learn_steps"] == 9 == t.optimizer.step_count and out["transitions"] == 192 and len(replay) == 100
+    assert bool(torch.isfinite(torch.from_numpy(out["losses"])).all()) and out["tallies"][0] >= 32
+    t2, sim2, replay2, out2 = once()
+    assert_same(snapshot(t, sim, replay), snapshot(t2, sim2, replay2))
+    assert (out["losses"] == out2["losses"]).all()
+
+
+def test_refusals(tmp_path):
+    from porl_amd.buffer.device_replay import DeviceReplay
+    from porl_amd.env import DiscreteLidarNavSim, NavWorld
+    from porl_amd.train.dqn_per_trainer import PERTrainer
+    from porl_amd.train.qr_dqn_trainer import QRDQNTrainer
+    from porl_amd.train.vector_online import train_vectorized
+    sim = make_sim()
+    per = PERTrainer(S, A, 0.99, device=DEV, batch_size=B, log_dir=str(tmp_path))
+    with pytest.raises(NotImplementedError, match=r"train_online\(Env\("):
+        per.train_vectorized(sim, 4)
+    qr = QRDQNTrainer(S, A, 0.99, device=DEV, num_quantiles=12, network_hidden_sizes=[64, 64])
+    with pytest.raises(NotImplementedError, match=r"train_online\(Env\("):
+        train_vectorized(qr, sim, 4)
+    t = make_trainer("dqn", tmp_path)
+    with pytest.raises(ValueError, match="auto_reset"):
+        t.train_vectorized(DiscreteLidarNavSim(NavWorld.lattice(), 8, n_beams=N_BEAMS), 4)
+    with pytest.raises(ValueError, match="observes"):
+        t.train_vectorized(DiscreteLidarNavSim(NavWorld.lattice(), 8, n_beams=20, auto_reset=True), 4)
+    with pytest.raises(ValueError, match="learning_starts"):
+        t.train_vectorized(sim, 4, replay=DeviceReplay(100, S, DEV), learning_starts=101)
+    assert t.optimizer.step_count == 0 and not hasattr(t, "_vec_steps")     # a refused call advanced nothing
