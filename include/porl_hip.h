@@ -946,6 +946,27 @@ int porl_per_sample_slots(const double* tree, int64_t capacity, const double* u,
 int porl_per_update_f32(double* tree, int64_t capacity, const int64_t* tree_idx, const float* td_abs, int32_t n,
                         double eps, double alpha, int32_t* stamp, void* stream);
 
+/* The two operations a loop needs that writes N rows per launch and never returns to the host (csrc/per_vector.hpp), one
+ * launch each, one block, no scratch; both bit-equal to the calls above for the same inputs.
+ * porl_per_fill_range: memory.add(td_error, ...) for the n data slots (first_slot + i) % capacity, i < n — the tree only,
+ *   the rows are the caller's: each leaf becomes (|td_error| + eps)^alpha and every ancestor of one of them is recomputed
+ *   as left + right, what porl_per_update leaves for those n tree indices with a constant td_error.  The leaves are one run
+ *   of tree indices (two when the ring wraps) and the parents of a run [a, b] are the run [(a-1)/2, (b-1)/2], so the call
+ *   writes about 2n + 4*levels nodes, not n*levels; no other node is written.  0 <= n <= capacity <= 2^40 (n == 0: PORL_OK,
+ *   no launch), 0 <= first_slot < capacity, td_error / eps / alpha finite; anything else is PORL_ERR_INVALID before a launch.
+ * porl_per_sample_keyed: porl_per_sample_slots whose uniforms are drawn in the kernel: sample i of draw `draw` uses
+ *   u_i = (double)(sm64(key ^ sm64((draw << 32) | i)) >> 11) * 2^-53,  key = sm64(seed ^ TAG),
+ *   TAG = 0xF08CDF1E9B01AC12 = sm64(0x5045524B45594544) ("PERKEYED"), sm64 as for porl_hindsight_pairs.  The tag keeps the
+ *   stream apart from what else the same seed keys: porl_qnet_select and the simulator key robot e by sm64(seed ^ sm64(e))
+ *   with e <= 2^40 + 2^24, and sm64 is a bijection; porl_sample_indices derives 32-bit Feistel round keys by another mixer.
+ *   Everything after u_i is porl_per_sample_slots' arithmetic (one shared device function).  Rejections as
+ *   porl_per_sample_slots, and 0 <= draw < 2^32 (batch is an int32 and fits its half of the counter). */
+int porl_per_fill_range(double* tree, int64_t capacity, int64_t first_slot, int64_t n, double td_error, double eps,
+                        double alpha, void* stream);
+int porl_per_sample_keyed(const double* tree, int64_t capacity, uint64_t seed, int64_t draw, int32_t batch,
+                          int64_t n_entries, double beta, int64_t* out_idx, int64_t* out_slots, float* out_w,
+                          float* out_wmean, double* scratch, void* stream);
+
 /* The lidar navigation task on the device (env/gazebo.py without ROS and Gazebo; csrc/navsim.hpp): a unicycle step and
  * a 2-D ray cast against a world of wall segments and pillars replace the physics and the laser.  One workgroup per
  * robot, one launch per call for any n, no host synchronisation.

@@ -24,7 +24,7 @@ SYMBOLS = [
     "porl_iql_policy_apply", "porl_iql_step", "porl_iql_policy_only_forward", "porl_iql_policy_only_step", "porl_iql_policy_prefetch", "porl_iql_forward_value", "porl_iql_forward_policy",
     "porl_iql_load_batch_cat", "porl_iql_load_batch_pairs", "porl_iql_bc_forward", "porl_iql_bc_step",
     "porl_gemm_f32", "porl_gemm_f32_group", "porl_adam_ema", "porl_ema", "porl_softmax_mask", "porl_gather_rows", "porl_sample_indices", "porl_epoch_indices", "porl_per_update", "porl_per_sample",
-    "porl_per_record", "porl_per_sample_slots", "porl_per_update_f32",
+    "porl_per_record", "porl_per_sample_slots", "porl_per_update_f32", "porl_per_fill_range", "porl_per_sample_keyed",
     "porl_prof_enable", "porl_prof_read", "porl_tune_set", "porl_tune_set_ptr", "porl_state2costmap", "porl_astar_label",
     "porl_signal_create", "porl_signal_destroy", "porl_signal_write", "porl_signal_wait_ge", "porl_iql_update_pipelined",
     "porl_qnet_create", "porl_qnet_destroy", "porl_qnet_param_floats", "porl_qnet_tensors",
@@ -218,6 +218,8 @@ def _declare(lib):
     lib.porl_per_record.argtypes = [vp, i64, i64, f64, f64, f64, vp, vp, i32, i64, f32, f32, C.POINTER(QnetMirror), vp]
     lib.porl_per_sample_slots.argtypes = [vp, i64, vp, i32, i64, f64, vp, vp, vp, vp, vp, vp]
     lib.porl_per_update_f32.argtypes = [vp, i64, vp, vp, i32, f64, f64, vp, vp]
+    lib.porl_per_fill_range.argtypes = [vp, i64, i64, i64, f64, f64, f64, vp]
+    lib.porl_per_sample_keyed.argtypes = [vp, i64, C.c_uint64, i64, i32, i64, f64, vp, vp, vp, vp, vp, vp]
     lib.porl_tune_set.argtypes = [C.c_char_p, C.c_int]
     lib.porl_iql_tune_set.argtypes = [vp, C.c_char_p, C.c_int]
     lib.porl_tune_set_ptr.argtypes = [C.c_char_p, vp]

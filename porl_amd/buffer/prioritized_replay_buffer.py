@@ -18,6 +18,13 @@ For the online loop (train/online.py) three one-launch forms sit beside them, bi
 `record` (= `add` + flush of that transition, the row carried in the kernel's arguments), `sample_slots` (= `sample`
 without the gathers: data slots for the step kernel, weights, their mean, tree indices) and `update_priorities_device`
 (= `update_priorities` on a device fp32 tensor, e.g. the step kernel's |TD errors|).
+
+For a loop that writes N rows per launch (train/vector_per.py; csrc/per_vector.hpp) the buffer is also a WRITER in
+DeviceReplay's protocol — `states`, `next_states`, `state_dim`, `mirror()`, `position`, `advance(n)` — so
+`DiscreteLidarNavSim.step(actions, replay=memory)` writes the rows and `advance(n)` gives the n new leaves the priority
+`priority_for_new` by one launch (`fill_range`, porl_per_fill_range: bit-equal to `add(priority_for_new, ...)` n times and
+a flush).  `sample_slots_keyed(batch_size, seed, draw)` is `sample_slots` with the uniforms drawn in the kernel from the
+counter stream (seed, draw, i): nothing is taken from Python's `random`, nothing is copied, nothing waits.
 """
 from __future__ import annotations
 
@@ -47,6 +54,10 @@ class PrioritizedReplayBuffer:
         self._pending = []                 # (slot, td_error, state, action, reward, next_state, done)
         self._store_c = None               # the store's arrays as porl_qnet_mirror (record)
         self._u = None                     # sample_slots: staging ring of the uniforms + the raw-weight scratch
+        self._raw = None                   # sample_slots_keyed: the raw-weight scratch
+        self.priority_for_new = 1.0        # advance(n): the td_error new rows enter with (a trainer's max_initial_priority)
+        if self.state_shape is not None:
+            self._alloc(None)
 
     # -- storage ---------------------------------------------------------------------------------------
     def _alloc(self, state):
@@ -216,6 +227,81 @@ class PrioritizedReplayBuffer:
         N.check(N.lib().porl_per_update_f32(N.ptr(self.tree), self.capacity, N.ptr(tree_indices), N.ptr(td_errors),
                                             tree_indices.numel(), self.epsilon, self.alpha, N.ptr(self._stamp),
                                             N.current_stream_ptr(self.device)), "porl_per_update_f32")
+
+    # -- the writer protocol of DeviceReplay and the keyed sampler (csrc/per_vector.hpp) ---------------------
+    def _need_store(self):
+        if self._store is None:
+            raise ValueError("the store is not allocated yet: construct the buffer with state_shape, or add a transition first")
+        return self._store
+
+    @property
+    def states(self):
+        return self._need_store()["states"]
+
+    @property
+    def next_states(self):
+        return self._need_store()["next_states"]
+
+    @property
+    def state_dim(self):
+        return self._need_store()["states"].shape[1]
+
+    @property
+    def position(self):
+        return self.data_pointer
+
+    def arrays(self):
+        """(states, actions, rewards, next_states, dones) in the shapes QnetEngine's row-sourced steps take."""
+        st = self._need_store()
+        return st["states"], st["actions"], st["rewards"].view(-1), st["next_states"], st["dones"].view(-1)
+
+    def mirror(self):
+        """The store's arrays as a porl_qnet_mirror (N.QnetMirror); pending host `add`s are flushed first, so a kernel
+        that writes through it writes after them."""
+        st = self._need_store()
+        if self._pending:
+            self._flush()
+        if self._store_c is None:
+            self._store_c = N.QnetMirror(*[C.c_void_p(st[k].data_ptr()) for k in
+                                           ("states", "next_states", "actions", "rewards", "dones")], self.capacity)
+        return self._store_c
+
+    def fill_range(self, first_slot, n, td_error):
+        """The tree half of `add(td_error, ...)` for the n data slots (first_slot + i) % capacity in one launch
+        (porl_per_fill_range): leaves (|td_error| + eps)^alpha, their ancestors recomputed.  Moves no pointer."""
+        if self._pending:
+            self._flush()
+        N.check(N.lib().porl_per_fill_range(N.ptr(self.tree), self.capacity, int(first_slot), int(n), float(td_error),
+                                            self.epsilon, self.alpha, N.current_stream_ptr(self.device)), "porl_per_fill_range")
+
+    def advance(self, n):
+        """A launch wrote n rows from `position` on (wrapping): give their leaves `priority_for_new` and move the ring."""
+        n = int(n)
+        if not 0 <= n <= self.capacity:
+            raise ValueError(f"advance({n}): a launch writes at most capacity = {self.capacity} rows")
+        self.fill_range(self.data_pointer, n, self.priority_for_new)
+        self.data_pointer = (self.data_pointer + n) % self.capacity
+        self.n_entries = min(self.n_entries + n, self.capacity)
+
+    def sample_slots_keyed(self, batch_size, seed, draw):
+        """`sample_slots` with the uniforms drawn in the kernel (porl_per_sample_keyed) -> (slots, is_weights, wmean,
+        tree_idx).  Same beta / frame_count bookkeeping; consumes nothing from Python's `random`."""
+        if self._pending:
+            self._flush()
+        if self.n_entries < 1:
+            raise ValueError("cannot sample from an empty buffer")
+        B = int(batch_size)
+        self.beta = np.min([1.0, self.beta_start + self.frame_count * (1.0 - self.beta_start) / self.beta_frames])
+        self.frame_count += 1
+        if self._raw is None or self._raw.numel() < B:
+            self._raw = torch.zeros(B, dtype=torch.float64, device=self.device)
+        idx = torch.empty(2, B, dtype=torch.int64, device=self.device)             # tree indices | data slots
+        w = torch.empty(B + 1, dtype=torch.float32, device=self.device)             # weights | their mean
+        N.check(N.lib().porl_per_sample_keyed(N.ptr(self.tree), self.capacity, int(seed) & (2 ** 64 - 1), int(draw), B,
+                                              self.n_entries, float(self.beta), N.ptr(idx[0]), N.ptr(idx[1]), N.ptr(w),
+                                              C.c_void_p(w.data_ptr() + 4 * B), N.ptr(self._raw),
+                                              N.current_stream_ptr(self.device)), "porl_per_sample_keyed")
+        return idx[1], w[:B], w[B:], idx[0]
 
     def __len__(self):
         return self.n_entries

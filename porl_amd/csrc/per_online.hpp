@@ -8,7 +8,8 @@
 //                            (|td| + eps)^alpha and its ancestors are recomputed from their children, leaf to root, by
 //                            one lane (a sequential chain of at most ceil(log2 capacity) + 1 fp64 additions).
 //   per_sample_slots_kernel  per_sample_kernel without the priorities: tree indices, data slots (the rows the step
-//                            kernel gathers itself), normalised weights and their mean as one fp32.
+//                            kernel gathers itself), normalised weights and their mean as one fp32.  Its body is a
+//                            device function of the uniform's source, which per_vector.hpp instantiates a second time.
 //   per_update_f32_kernel    the priority write-back in one block: stamp -> last writer sets the leaf -> ancestors level
 //                            by level, on the step kernel's fp32 |TD| widened to fp64.
 #pragma once
@@ -71,7 +72,10 @@ struct PerSampleSlotsArgs {
   double* raw;                 // (batch,) scratch: the raw weights
 };
 
-__global__ __launch_bounds__(256) void per_sample_slots_kernel(const PerSampleSlotsArgs a) {
+// The body of per_sample_slots_kernel with the uniform of sample i as u_of(i): the one copy of the arithmetic, shared with
+// per_sample_keyed_kernel (per_vector.hpp), which draws u_i itself.  One block of 256 lanes.
+template <class UOf>
+__device__ __forceinline__ void per_sample_slots_body(const PerSampleSlotsArgs& a, UOf u_of) {
   __shared__ double red[256];
   const int64_t size = 2 * a.capacity - 1;
   const double total = a.tree[0];
@@ -79,7 +83,7 @@ __global__ __launch_bounds__(256) void per_sample_slots_kernel(const PerSampleSl
   double wmax = 0.0;
   for (int i = threadIdx.x; i < a.batch; i += 256) {
     const double lo = segment * (double)i, hi = segment * (double)(i + 1);
-    double s = lo + (hi - lo) * a.u[i];                       // random.uniform(a, b) = a + (b - a) * random()
+    double s = lo + (hi - lo) * u_of(i);                      // random.uniform(a, b) = a + (b - a) * random()
     int64_t idx = 0;
     for (;;) {
       const int64_t left = 2 * idx + 1;
@@ -108,6 +112,10 @@ __global__ __launch_bounds__(256) void per_sample_slots_kernel(const PerSampleSl
     for (int i = 0; i < a.batch; ++i) sum += a.raw[i];        // one fixed order
     *a.out_wmean = (float)(sum / wmax / (double)a.batch);
   }
+}
+
+__global__ __launch_bounds__(256) void per_sample_slots_kernel(const PerSampleSlotsArgs a) {
+  per_sample_slots_body(a, [&a](int i) { return a.u[i]; });
 }
 
 // One block.  A tree index outside the leaves is skipped (nothing is read or written through it).

@@ -22,6 +22,7 @@
 #include "dist_losses.hpp"
 #include "online.hpp"
 #include "per_online.hpp"
+#include "per_vector.hpp"
 #include "bcq_mask.hpp"
 #include "astar.hpp"
 #include "episodes.hpp"
@@ -874,3 +875,4 @@ int porl_prof_read(porl_prof_entry* out, int max_entries) {
 #include "colstats_api.inc"
 #include "navsim_api.inc"
 #include "navsim_discrete_api.inc"
+#include "per_vector_api.inc"

@@ -53,6 +53,12 @@ class PERTrainer(CQLTrainer):
         mem.update_priorities(tree_idx, td_abs)
         return read_losses(self)
 
+    def train_vectorized_per(self, sim, n_steps, **kw):
+        """N robots of the discrete lidar task per step, this trainer's memory and learn step, no host synchronisation inside
+        the loop: train/vector_per.py.  (`train_vectorized`, the plain-Q loop, keeps turning this trainer away.)"""
+        from .vector_per import train_vectorized_per
+        return train_vectorized_per(self, sim, n_steps, **kw)
+
     def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
         """dqn_per_trainer.py:127-175: memory.add(max_initial_priority, ...) and a learn step once len(memory) >=
         batch_size; the loop of train/online.py.  On the one-launch step kernel with this class's own learn /

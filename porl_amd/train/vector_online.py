@@ -19,8 +19,9 @@ episode's place: after every block, on the host and without waiting, epsilon = m
 and the target network is synchronised after block b when b % update_target_freq == 0 (b counts from 0, as the reference's
 episode number does).
 
-Plain-Q trainers only: CQLTrainer, DQNTrainer, DDQNTrainer, DDDQNTrainer.  PER, BCQ and the distributional trainers
-(C51, QR-DQN, IQN) run in this task through their own `train_online(Env(...))`.
+Plain-Q trainers only: CQLTrainer, DQNTrainer, DDQNTrainer, DDDQNTrainer.  PERTrainer has the same loop around its own
+memory as `train_vectorized_per` (train/vector_per.py, which shares `check_sim`, `check_starts` and `end_of_step` below);
+BCQ and the distributional trainers (C51, QR-DQN, IQN) run in this task through their own `train_online(Env(...))`.
 """
 from __future__ import annotations
 
@@ -71,6 +72,38 @@ def learn_step(trainer, replay, seed, draw):
     trainer.optimizer.step_count = hp.step
 
 
+def check_sim(eng, sim, n_steps, block, learn_per_step, who):
+    """The argument checks the vectorised loops share (`who` names the loop in the one message that names it)."""
+    S = sim.obs_dim
+    if not sim.auto_reset:
+        raise ValueError(f"{who} needs a simulator with auto_reset=True")
+    if S != eng.cfg.state_dim or sim.n_actions != eng.cfg.n_actions:
+        raise ValueError(f"the simulator observes {S} floats and takes {sim.n_actions} actions; the trainer's network maps "
+                         f"{eng.cfg.state_dim} to {eng.cfg.n_actions}")
+    if sim.state.device != eng.device:
+        raise ValueError(f"simulator on {sim.state.device}, trainer on {eng.device}")
+    if n_steps < 1 or block < 1 or learn_per_step < 0:
+        raise ValueError("n_steps and block must be positive, learn_per_step not negative")
+
+
+def check_starts(trainer, learning_starts, capacity):
+    """The first buffer size at which a learn step runs: never below batch_size, never above `capacity`."""
+    starts = max(trainer.batch_size, int(trainer.training_learning_step if learning_starts is None else learning_starts))
+    if starts > capacity:
+        raise ValueError(f"learning_starts {starts} > replay capacity {capacity}: no learn step would ever run")
+    return starts
+
+
+def end_of_step(trainer, t, block):
+    """Close act-step t: advance the counter and, when a block ends, apply the reference's per-episode schedule."""
+    trainer._vec_steps = t + 1
+    if trainer._vec_steps % block == 0:
+        b = trainer._vec_steps // block - 1
+        trainer.epsilon = max(trainer.epsilon_min, trainer.epsilon * trainer.epsilon_decay)
+        if b % trainer.update_target_freq == 0:
+            trainer.sync_target()
+
+
 def train_vectorized(trainer, sim, n_steps, replay=None, learn_per_step=1, learning_starts=None, block=32, seed=0):
     """Run `n_steps` iterations of act -> step -> learn (module docstring) with `sim`, a DiscreteLidarNavSim with
     auto_reset=True whose observation and action count are the trainer's.  `replay`: a DeviceReplay (default: one of the
@@ -82,23 +115,12 @@ def train_vectorized(trainer, sim, n_steps, replay=None, learn_per_step=1, learn
     _refuse(trainer)
     eng = trainer._engine
     N_, S = sim.n_envs, sim.obs_dim
-    if not sim.auto_reset:
-        raise ValueError("train_vectorized needs a simulator with auto_reset=True")
-    if S != eng.cfg.state_dim or sim.n_actions != eng.cfg.n_actions:
-        raise ValueError(f"the simulator observes {S} floats and takes {sim.n_actions} actions; the trainer's network maps "
-                         f"{eng.cfg.state_dim} to {eng.cfg.n_actions}")
-    if sim.state.device != eng.device:
-        raise ValueError(f"simulator on {sim.state.device}, trainer on {eng.device}")
-    if n_steps < 1 or block < 1 or learn_per_step < 0:
-        raise ValueError("n_steps and block must be positive, learn_per_step not negative")
+    check_sim(eng, sim, n_steps, block, learn_per_step, "train_vectorized")
     if replay is None:
         replay = getattr(trainer, "device_replay", None)
         if replay is None:
             replay = DeviceReplay(max(int(getattr(trainer.replay_buffer, "capacity", 100000)), N_), S, eng.device)
-    B = trainer.batch_size
-    starts = max(B, int(trainer.training_learning_step if learning_starts is None else learning_starts))
-    if starts > replay.capacity:
-        raise ValueError(f"learning_starts {starts} > replay capacity {replay.capacity}: no learn step would ever run")
+    starts = check_starts(trainer, learning_starts, replay.capacity)
     trainer.device_replay = replay
     eng._ensure_bound()
     if bool((sim.counters[:, 2] & 0xff != 0).any()):                 # before the loop: robots that are not running
@@ -119,11 +141,6 @@ def train_vectorized(trainer, sim, n_steps, replay=None, learn_per_step=1, learn
                 trainer._draws += 1
                 loss_log[n_learn:n_learn + 1].copy_(eng.stats[:1])
                 n_learn += 1
-        trainer._vec_steps = t + 1
-        if trainer._vec_steps % block == 0:                           # a block ends: the reference's per-episode schedule
-            b = trainer._vec_steps // block - 1
-            trainer.epsilon = max(trainer.epsilon_min, trainer.epsilon * trainer.epsilon_decay)
-            if b % trainer.update_target_freq == 0:
-                trainer.sync_target()
+        end_of_step(trainer, t, block)                                # a block ends: the reference's per-episode schedule
     host = torch.cat([loss_log[:n_learn].double(), sim.tallies.sum(0)]).cpu().numpy()      # the one read-back
     return dict(losses=host[:n_learn].astype("float32"), tallies=host[n_learn:], transitions=N_ * n_steps, learn_steps=n_learn)
