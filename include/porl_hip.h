@@ -454,6 +454,14 @@ typedef struct porl_dist_head {
 int porl_qnet_dist_learn(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
                          const float* next_states, int64_t n_rs, const float* dones, const int64_t* idx, int32_t batch,
                          const porl_qnet_hyper* hp, const porl_dist_head* head, void* stream);
+/* porl_qnet_dist_learn on `batch` distinct rows of the first n_rows rows of the replay arrays: row b is position b of the
+ * keyed permutation (seed, draw) of [0, n_rows), the rows porl_sample_indices(n_rows, batch, seed, draw) writes, drawn
+ * inside the gather launch — no index array and no extra launch; bit-equal to porl_sample_indices followed by
+ * porl_qnet_dist_learn.  batch <= n_rows <= 2^40.  Every argument is checked before the first launch. */
+int porl_qnet_dist_learn_sampled(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
+                                 const float* next_states, int64_t n_rs, const float* dones, int64_t n_rows, uint64_t seed,
+                                 uint64_t draw, int32_t batch, const porl_qnet_hyper* hp, const porl_dist_head* head,
+                                 void* stream);
 int porl_qnet_sync_target(porl_qnet* h, void* stream);
 /* q_network(states) (which=0) or target_network(states) (which=1) -> (batch, n_actions) */
 int porl_qnet_forward(porl_qnet* h, int which, const float* states, int64_t s_rs, int32_t batch,
@@ -1091,9 +1099,25 @@ int porl_qnet_select(const float* q, int64_t q_rs, int32_t n_actions, int64_t n,
                      int64_t env_offset, uint64_t t, int64_t* out, void* stream);
 /* porl_qnet_forward on n rows of states, walked in chunks of the engine's max_batch, into the caller's scratch q (n,
  * n_actions), then porl_qnet_select on it: acting for n robots from one call.  Plain-Q networks only (DQN, Double DQN,
- * Dueling through the composed output layer, CQL); C51, QR-DQN and IQN are out of scope. */
+ * Dueling through the composed output layer, CQL); C51 and QR-DQN have porl_qnet_act_rows_dist, IQN is out of scope. */
 int porl_qnet_act_rows(porl_qnet* h, int which, const float* states, int64_t s_rs, int64_t n, float* q, int64_t q_rs,
                        double epsilon, uint64_t seed, int64_t env_offset, uint64_t t, int64_t* out, void* stream);
+/* Epsilon-greedy over the outputs of a distributional network: z (n, n_actions * n_sub) fp32 with row stride z_rs, action
+ * a in columns [a * n_sub, (a + 1) * n_sub).  One value per action — PORL_DIST_QR: the mean of the n_sub quantiles;
+ * PORL_DIST_C51: sum_n softmax(z[a, :])_n support[n] — summed in the order the loss heads rank the next state's actions
+ * by (lane-strided partials of a 64-lane wave, then the xor butterfly), so acting and bootstrapping agree.  The n_actions
+ * values go to q (n, n_actions) with row stride q_rs and the action to out (n) int64, both always, also when the robot
+ * explores; the action is porl_qnet_select's rule on those values, with the same key and draws.  Of head only kind,
+ * n_actions (<= 64), n_sub (<= 256; C51: >= 2) and support (C51: n_sub device floats) are read.  Stateless; one launch;
+ * every argument is checked before it. */
+int porl_dist_select(const float* z, int64_t z_rs, const porl_dist_head* head, int64_t n, float* q, int64_t q_rs,
+                     double epsilon, uint64_t seed, int64_t env_offset, uint64_t t, int64_t* out, void* stream);
+/* porl_qnet_act_rows for a C51 / QR-DQN network: n rows of states in chunks of the engine's max_batch, each chunk staged,
+ * forwarded, and handed to porl_dist_select's kernel where the forward left its output rows in the workspace — the
+ * n x n_actions * n_sub outputs are never copied out.  head->n_actions * head->n_sub must equal the engine's outputs. */
+int porl_qnet_act_rows_dist(porl_qnet* h, int which, const float* states, int64_t s_rs, int64_t n, const porl_dist_head* head,
+                            float* q, int64_t q_rs, double epsilon, uint64_t seed, int64_t env_offset, uint64_t t,
+                            int64_t* out, void* stream);
 
 /* Experiment knobs (scheduling only, never the mathematics).  "gemm_lds_pad": extra dynamic LDS bytes per GEMM block,
  * limiting how many blocks share a CU.  "qnet_fused": 0 forces the multi-launch CQL path.  porl_tune_set sets the process

@@ -45,6 +45,7 @@ SYMBOLS = [
     "porl_colstats_workspace", "porl_col_stats", "porl_affine_cols",
     "porl_nav_scan", "porl_nav_reset", "porl_nav_step",
     "porl_nav_dreset", "porl_nav_dstep", "porl_qnet_select", "porl_qnet_act_rows",
+    "porl_dist_select", "porl_qnet_act_rows_dist", "porl_qnet_dist_learn_sampled",
 ]
 
 
@@ -333,6 +334,11 @@ def _declare(lib):
                                    vp, vp, vp, i64, vp, i64, vp, vp, vp, C.POINTER(QnetMirror), i64, vp, vp, i64, vp]
     lib.porl_qnet_select.argtypes = [vp, i64, i32, i64, f64, C.c_uint64, i64, C.c_uint64, vp, vp]
     lib.porl_qnet_act_rows.argtypes = [vp, C.c_int, vp, i64, i64, vp, i64, f64, C.c_uint64, i64, C.c_uint64, vp, vp]
+    lib.porl_dist_select.argtypes = [vp, i64, C.POINTER(DistHead), i64, vp, i64, f64, C.c_uint64, i64, C.c_uint64, vp, vp]
+    lib.porl_qnet_act_rows_dist.argtypes = [vp, C.c_int, vp, i64, i64, C.POINTER(DistHead), vp, i64, f64, C.c_uint64, i64,
+                                            C.c_uint64, vp, vp]
+    lib.porl_qnet_dist_learn_sampled.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, i64, C.c_uint64, C.c_uint64, i32,
+                                                 C.POINTER(QnetHyper), C.POINTER(DistHead), vp]
     lib.porl_prof_enable.argtypes = [C.c_int]
     lib.porl_prof_read.argtypes = [C.POINTER(ProfEntry), C.c_int]
     for name in SYMBOLS:

@@ -1093,18 +1093,22 @@ __global__ __launch_bounds__(256) void cql_loss_kernel(const CqlLossArgs a) {
 
 // Minibatch gather of the multi-launch Q-network path: rows idx[b] of the replay arrays -> the engine's staging buffers
 // (states / next states zero padded to ld columns).  grid (ceil(B * ld / 256)), the first B threads also move the
-// row's action, reward and done flag.
+// row's action, reward and done flag.  With samp_n > 0 (callers zero-initialise the struct: off) the rows are drawn here:
+// row b = feistel_index(samp_n, b, samp_seed, samp_step, samp_hb), the rows of porl_sample_indices, and idx is not read.
 struct QnetGatherArgs {
   const float* states; const float* next_states; long s_rs, n_rs;
   const int64_t* actions; const float* rew; const float* done; const int64_t* idx;
   float* xs; float* xn; int64_t* act_out; float* rew_out; float* done_out;
   int B, S, ld;
+  int samp_hb;
+  int64_t samp_n; uint64_t samp_seed, samp_step;
 };
 __global__ __launch_bounds__(256) void qnet_gather_kernel(const QnetGatherArgs a) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)a.B * a.ld) return;
   const int b = (int)(i / a.ld), c = (int)(i - (long)b * a.ld);
-  const long row = a.idx ? a.idx[b] : (long)b;
+  const long row = a.samp_n > 0 ? (long)feistel_index(a.samp_n, b, a.samp_seed, a.samp_step, a.samp_hb)
+                                : (a.idx ? a.idx[b] : (long)b);
   a.xs[i] = c < a.S ? a.states[row * a.s_rs + c] : 0.f;
   a.xn[i] = c < a.S ? a.next_states[row * a.n_rs + c] : 0.f;
   if (c == 0) { a.act_out[b] = a.actions[row]; a.rew_out[b] = a.rew[row]; a.done_out[b] = a.done[row]; }

@@ -1,11 +1,11 @@
 // The discrete lidar navigation task and acting for N robots without a read-back (porl_nav_dreset, porl_nav_dstep,
-// porl_qnet_select, porl_qnet_act_rows): the host side of csrc/navsim_discrete.hpp.  Included by porl_api.hip behind
-// navsim_api.inc and qnet_api.inc, whose checks it shares.  Every argument is judged before the first device call; no
-// allocation and no synchronisation.
+// porl_qnet_select, porl_qnet_act_rows, porl_dist_select, porl_qnet_act_rows_dist): the host side of
+// csrc/navsim_discrete.hpp and csrc/dist_act.hpp.  Included by porl_api.hip behind navsim_api.inc and qnet_api.inc, whose
+// checks it shares.  Every argument is judged before the first device call; no allocation and no synchronisation.
 //
-// porl_qnet_act_rows covers the plain-Q epilogue only — DQN, Double DQN, Dueling (through the composed output layer) and
-// CQL.  The distributional heads (C51, QR-DQN) and IQN are out of scope here: their trainers act through porl_qnet_act /
-// porl_iqn_act.
+// porl_qnet_act_rows covers the plain-Q epilogue — DQN, Double DQN, Dueling (through the composed output layer) and CQL;
+// porl_qnet_act_rows_dist the distributional heads on the same engine (C51, QR-DQN), whose n x A*NS outputs stay in the
+// workspace.  IQN is out of scope here: its trainer acts through porl_iqn_act.
 
 namespace {
 
@@ -54,6 +54,27 @@ int select_launch(const float* q, int64_t q_rs, int32_t n_actions, int64_t n, do
   hipLaunchKernelGGL(qnet_select_kernel, dim3((unsigned)((n + SELECT_THREADS - 1) / SELECT_THREADS)), dim3(SELECT_THREADS), 0, s, q,
                      (long long)q_rs, (int)n_actions, (long long)n, epsilon, seed, (long long)env_offset, (long long)t,
                      reinterpret_cast<long long*>(out));
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+// the head rules of porl_qnet_dist_learn (n_out: the network's outputs, < 0: no network), then select_check's
+int dist_select_check(const porl_dist_head* head, int64_t n_out, int64_t n, const float* q, int64_t q_rs, double epsilon,
+                      int64_t env_offset, uint64_t t, const int64_t* out) {
+  if (!head) PORL_FAIL(PORL_ERR_INVALID, "null head");
+  PORL_TRY(dist_head_ok(head, n_out));
+  return select_check(q, q_rs, head->n_actions, n, epsilon, env_offset, t, out);
+}
+
+int dist_select_launch(const float* z, int64_t z_rs, const porl_dist_head* head, int64_t n, float* q, int64_t q_rs,
+                       double epsilon, uint64_t seed, int64_t env_offset, uint64_t t, int64_t* out, hipStream_t s) {
+  DistSelectArgs a{};
+  a.z = z; a.z_rs = (long long)z_rs; a.support = head->support;
+  a.q = q; a.q_rs = (long long)q_rs; a.out = reinterpret_cast<long long*>(out);
+  a.n = (long long)n; a.env_offset = (long long)env_offset; a.t = (long long)t;
+  a.epsilon = epsilon; a.seed = seed;
+  a.kind = head->kind == PORL_DIST_QR ? 0 : 1; a.A = head->n_actions; a.NS = head->n_sub;
+  hipLaunchKernelGGL(dist_select_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, a);
   PORL_HIP(hipGetLastError());
   return PORL_OK;
 }
@@ -155,6 +176,41 @@ int porl_qnet_act_rows(porl_qnet* h, int which, const float* states, int64_t s_r
     PORL_TRY(porl_qnet_forward(h, which, states + r * s_rs, s_rs, nb, q + r * q_rs, q_rs, stream));
   }
   return select_launch(q, q_rs, h->cfg.n_actions, n, epsilon, seed, env_offset, t, out, (hipStream_t)stream);
+}
+
+int porl_dist_select(const float* z, int64_t z_rs, const porl_dist_head* head, int64_t n, float* q, int64_t q_rs,
+                     double epsilon, uint64_t seed, int64_t env_offset, uint64_t t, int64_t* out, void* stream) {
+  if (!z) PORL_FAIL(PORL_ERR_INVALID, "null outputs z");
+  PORL_TRY(dist_select_check(head, -1, n, q, q_rs, epsilon, env_offset, t, out));
+  if (z_rs < (int64_t)head->n_actions * head->n_sub || z_rs > NAV_MAX_STRIDE)
+    PORL_FAIL(PORL_ERR_INVALID, "z_rs %lld: a row of outputs is %d x %d floats", (long long)z_rs, head->n_actions, head->n_sub);
+  DevGuard _dg(device_of(out));
+  return dist_select_launch(z, z_rs, head, n, q, q_rs, epsilon, seed, env_offset, t, out, (hipStream_t)stream);
+}
+
+// chunks of max_batch: stage the states, forward, and the select kernel on the output rows where the forward left them
+int porl_qnet_act_rows_dist(porl_qnet* h, int which, const float* states, int64_t s_rs, int64_t n, const porl_dist_head* head,
+                            float* q, int64_t q_rs, double epsilon, uint64_t seed, int64_t env_offset, uint64_t t,
+                            int64_t* out, void* stream) {
+  PORL_TRY(qnet_ready(h, false));
+  if (which != 0 && which != 1) PORL_FAIL(PORL_ERR_INVALID, "which %d: 0 online, 1 target", which);
+  if (!states) PORL_FAIL(PORL_ERR_INVALID, "null states");
+  if (s_rs < h->cfg.state_dim || s_rs > NAV_MAX_STRIDE)
+    PORL_FAIL(PORL_ERR_INVALID, "s_rs %lld: a state is %d floats", (long long)s_rs, h->cfg.state_dim);
+  const int L = h->cfg.n_hidden;
+  PORL_TRY(dist_select_check(head, h->cfg.n_actions, n, q, q_rs, epsilon, env_offset, t, out));
+  DevGuard _dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t mb = h->cfg.max_batch;
+  for (int64_t r = 0; r < n; r += mb) {
+    const int32_t nb = (int32_t)std::min(mb, n - r);
+    PORL_TRY(porl_qnet_load_batch(h, nb, states + r * s_rs, s_rs, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, stream));
+    h->batch = 0;
+    float* z = nullptr;
+    PORL_TRY(qnet_forward_one(h, which ? h->buf.params_tgt : h->buf.params, h->buf.workspace + h->ws.xs, false, nb, s, &z));
+    PORL_TRY(dist_select_launch(z, h->ld[L], head, nb, q + r * q_rs, q_rs, epsilon, seed, env_offset + r, t, out + r, s));
+  }
+  return PORL_OK;
 }
 
 }  // extern "C"

@@ -31,6 +31,7 @@
 #include "colstats.hpp"
 #include "navsim.hpp"
 #include "navsim_discrete.hpp"
+#include "dist_act.hpp"
 
 using namespace porl;
 

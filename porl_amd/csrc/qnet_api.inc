@@ -323,7 +323,8 @@ static QnetRows qnet_staged_rows(const porl_qnet* h) {
   return r;
 }
 
-// rows idx[b] of the caller's arrays into the staging buffers: one launch
+// rows idx[b] of the caller's arrays — or, with samp_n > 0, the rows the keyed permutation draws — into the staging
+// buffers: one launch
 static int qnet_gather(porl_qnet* h, const QnetRows& r, int B, hipStream_t s) {
   float* W = h->buf.workspace;
   QnetGatherArgs a{};
@@ -332,6 +333,10 @@ static int qnet_gather(porl_qnet* h, const QnetRows& r, int B, hipStream_t s) {
   a.xs = W + h->ws.xs; a.xn = W + h->ws.xn; a.act_out = reinterpret_cast<int64_t*>(W + h->ws.actions);
   a.rew_out = W + h->ws.rew; a.done_out = W + h->ws.done;
   a.B = B; a.S = h->cfg.state_dim; a.ld = h->Sp;
+  if (r.samp_n > 0) {
+    a.samp_n = r.samp_n; a.samp_seed = r.samp_seed; a.samp_step = r.samp_step; a.samp_hb = feistel_half_bits(r.samp_n);
+    a.idx = nullptr;
+  }
   hipLaunchKernelGGL(qnet_gather_kernel, dim3((unsigned)(((long)B * h->Sp + 255) / 256)), dim3(256), 0, s, a);
   PORL_HIP(hipGetLastError());
   h->batch = B;
@@ -879,28 +884,36 @@ int porl_qnet_bcq_learn_sampled(porl_qnet* h, porl_qnet* beh, const float* state
 // porl_qnet_apply + porl_reduce_mean without the copies between them: one gather, the forwards grouped per layer, the loss
 // head reading the padded output rows and writing dL/dz where the backward chain reads it (the head zero-fills columns
 // A*N .. ld-1, as pack_kernel did), the mean into stats[0].  Same kernels on the same numbers: bit-equal results.
-int porl_qnet_dist_learn(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
-                         const float* next_states, int64_t n_rs, const float* dones, const int64_t* idx, int32_t batch,
-                         const porl_qnet_hyper* hp, const porl_dist_head* head, void* stream) {
-  PORL_TRY(qnet_ready(h, false));
-  if (!hp || !head || !states || !actions || !rewards || !next_states || !dones) PORL_FAIL(PORL_ERR_INVALID, "null argument");
-  PORL_TRY(qnet_batch_ok(h, batch));
-  if (s_rs < h->cfg.state_dim || n_rs < h->cfg.state_dim) PORL_FAIL(PORL_ERR_INVALID, "row stride below state_dim %d", h->cfg.state_dim);
+// The head rules porl_qnet_dist_learn and the acting entry points share; n_out: the network's outputs (< 0: no network)
+static int dist_head_ok(const porl_dist_head* head, int64_t n_out) {
   if (head->kind != PORL_DIST_QR && head->kind != PORL_DIST_C51) PORL_FAIL(PORL_ERR_INVALID, "unknown head kind %d", head->kind);
   PORL_TRY(qnet_in_range("n_sub", head->n_sub, DIST_MAX_N));
-  if (head->n_actions < 1 || (int64_t)head->n_actions * head->n_sub != h->cfg.n_actions)
-    PORL_FAIL(PORL_ERR_INVALID, "n_actions %d x n_sub %d != the network's %d outputs", head->n_actions, head->n_sub, h->cfg.n_actions);
+  if (n_out >= 0 && (head->n_actions < 1 || (int64_t)head->n_actions * head->n_sub != n_out))
+    PORL_FAIL(PORL_ERR_INVALID, "n_actions %d x n_sub %d != the network's %d outputs", head->n_actions, head->n_sub, (int)n_out);
   if (head->kind == PORL_DIST_C51) {
     if (head->n_sub < 2 || !(head->v_max > head->v_min)) PORL_FAIL(PORL_ERR_INVALID, "C51 needs n_sub >= 2 and v_max > v_min");
     if (!head->support) PORL_FAIL(PORL_ERR_INVALID, "C51 needs the support (null)");
   }
+  return PORL_OK;
+}
+
+// the step on `rows` (idx, or with sampled the keyed draw of rows.samp_n rows inside the gather launch)
+static int qnet_dist_learn_rows(porl_qnet* h, const QnetRows& rows, bool sampled, int32_t batch, const porl_qnet_hyper* hp,
+                                const porl_dist_head* head, void* stream) {
+  PORL_TRY(qnet_ready(h, false));
+  if (!hp || !head || !rows.states || !rows.actions || !rows.rewards || !rows.next_states || !rows.dones)
+    PORL_FAIL(PORL_ERR_INVALID, "null argument");
+  PORL_TRY(qnet_batch_ok(h, batch));
+  if (sampled) PORL_TRY(qnet_n_rows_ok(rows.samp_n, batch));
+  if (rows.s_rs < h->cfg.state_dim || rows.n_rs < h->cfg.state_dim) PORL_FAIL(PORL_ERR_INVALID, "row stride below state_dim %d", h->cfg.state_dim);
+  PORL_TRY(dist_head_ok(head, h->cfg.n_actions));
   if (hp->step < 1) PORL_FAIL(PORL_ERR_INVALID, "adam step must be >= 1");
   DevGuard _dg(h->device);
   hipStream_t s = (hipStream_t)stream;
   float* W = h->buf.workspace;
   const int L = h->cfg.n_hidden, B = batch, A = head->n_actions, N = head->n_sub;
   const bool qr = head->kind == PORL_DIST_QR;
-  PORL_TRY(qnet_gather(h, QnetRows{states, s_rs, actions, rewards, next_states, n_rs, dones, idx}, B, s));
+  PORL_TRY(qnet_gather(h, rows, B, s));
   // online net on s (kept), target net on s', QR-DQN: online net on s' — one launch per layer
   float* dst[3][PORL_MAX_HIDDEN + 1];
   for (int l = 0; l <= L; ++l) { dst[0][l] = W + h->ws.act[l]; dst[1][l] = W + h->ws.tmp[l & 1]; dst[2][l] = W + h->ws.tmp2[l & 1]; }
@@ -928,6 +941,23 @@ int porl_qnet_dist_learn(porl_qnet* h, const float* states, int64_t s_rs, const 
   }
   PORL_TRY(qnet_backward_chain(h, dz, B, s));
   return qnet_adam(h, hp, s);
+}
+
+int porl_qnet_dist_learn(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
+                         const float* next_states, int64_t n_rs, const float* dones, const int64_t* idx, int32_t batch,
+                         const porl_qnet_hyper* hp, const porl_dist_head* head, void* stream) {
+  const QnetRows rows{states, s_rs, actions, rewards, next_states, n_rs, dones, idx};
+  return qnet_dist_learn_rows(h, rows, false, batch, hp, head, stream);
+}
+
+// porl_qnet_dist_learn on the rows feistel_index(n_rows, b, seed, draw, hb) gives — porl_sample_indices' rows — drawn inside
+// the gather launch: no index tensor, no extra launch
+int porl_qnet_dist_learn_sampled(porl_qnet* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
+                                 const float* next_states, int64_t n_rs, const float* dones, int64_t n_rows, uint64_t seed,
+                                 uint64_t draw, int32_t batch, const porl_qnet_hyper* hp, const porl_dist_head* head,
+                                 void* stream) {
+  const QnetRows rows{states, s_rs, actions, rewards, next_states, n_rs, dones, nullptr, n_rows, seed, draw};
+  return qnet_dist_learn_rows(h, rows, true, batch, hp, head, stream);
 }
 
 int porl_qnet_sync_target(porl_qnet* h, void* stream) {

@@ -807,6 +807,28 @@ class QnetEngine:
                 "porl_qnet_act_rows")
         return out
 
+    def act_rows_dist(self, states, head, epsilon, seed, t, env_offset=0, q=None, out=None, which=0):
+        """act_rows for a C51 / QR-DQN network (N.DistHead `head`, porl_qnet_act_rows_dist): the batched forward in chunks
+        of max_batch, each chunk's output rows read in the workspace by dist_select's kernel — the (n, A * n_sub) outputs
+        are never copied out.  `q` (n, A) receives the action values."""
+        self._ensure_bound()
+        x = self._states(states)
+        q, out, q_rs = _dist_select_args(x.shape[0], head, q, out, self.device)
+        N.check(self._lib.porl_qnet_act_rows_dist(self._h, int(which), N.ptr(x), x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1]),
+                                                  x.shape[0], C.byref(head), N.ptr(q), q_rs, float(epsilon),
+                                                  int(seed) & (2 ** 64 - 1), int(env_offset), int(t), N.ptr(out),
+                                                  N.current_stream_ptr(self.device)), "porl_qnet_act_rows_dist")
+        return out
+
+    def dist_learn_sampled(self, hp, states, actions, rewards, next_states, dones, n_rows, batch, seed, draw, head):
+        """dist_learn on the rows engine.sample_indices(n_rows, batch, seed, draw) would give, drawn inside the gather
+        launch (porl_qnet_dist_learn_sampled); the mean loss lands in stats[0]."""
+        args = self._replay(batch, states, actions, rewards, next_states, dones, n_rows)
+        N.check(self._lib.porl_qnet_dist_learn_sampled(self._h, *args, int(n_rows), int(seed), int(draw), int(batch),
+                                                       C.byref(hp), C.byref(head), N.current_stream_ptr(self.device)),
+                "porl_qnet_dist_learn_sampled")
+        return batch
+
     def penalty(self, states, actions):
         self._ensure_bound()
         states = self._states(states)
@@ -987,6 +1009,34 @@ def qnet_select(q, epsilon, seed, t, env_offset=0, out=None):
     out, q_rs = _select_args(q, out)
     N.check(N.lib().porl_qnet_select(N.ptr(q), q_rs, q.shape[1], q.shape[0], float(epsilon), int(seed) & (2 ** 64 - 1),
                                      int(env_offset), int(t), N.ptr(out), N.current_stream_ptr(q)), "porl_qnet_select")
+    return out
+
+
+def _dist_select_args(n, head, q, out, device):
+    """The (n, A) value table (a scratch one when None) and the (n,) int64 actions of a distributional select."""
+    A = int(head.n_actions)
+    if q is None:
+        q = torch.empty(n, max(A, 1), dtype=torch.float32, device=device)
+    if q.dim() != 2 or q.shape != (n, A) or q.device != device:
+        raise RuntimeError(f"q: expected ({n}, {A}) on {device}, got {tuple(q.shape)} on {q.device}")
+    out, q_rs = _select_args(q, out)
+    return q, out, q_rs
+
+
+def dist_select(z, head, epsilon, seed, t, env_offset=0, q=None, out=None):
+    """Epsilon-greedy actions (n,) int64 on the device from the outputs z (n, A * n_sub) of a distributional network
+    (N.DistHead `head`; porl_dist_select): one value per action — the quantile mean (QR-DQN) or the expectation of the
+    softmax over the atoms (C51), in the loss heads' summation order — written to `q` (n, A) when given, then qnet_select's
+    rule on them with the same key and draws; nothing is read back."""
+    if z.dim() != 2 or z.dtype != torch.float32 or z.device.type != "cuda" or (z.shape[1] > 1 and z.stride(1) != 1):
+        raise RuntimeError("z: need a (n, n_actions * n_sub) float32 table with unit column stride on a HIP device")
+    n, w = z.shape[0], int(head.n_actions) * int(head.n_sub)
+    if z.shape[1] != w:
+        raise RuntimeError(f"z: expected ({n}, {head.n_actions} x {head.n_sub}), got {tuple(z.shape)}")
+    q, out, q_rs = _dist_select_args(n, head, q, out, z.device)
+    z_rs = z.stride(0) if n > 1 else max(z.stride(0), w)
+    N.check(N.lib().porl_dist_select(N.ptr(z), z_rs, C.byref(head), n, N.ptr(q), q_rs, float(epsilon), int(seed) & (2 ** 64 - 1),
+                                     int(env_offset), int(t), N.ptr(out), N.current_stream_ptr(z)), "porl_dist_select")
     return out
 
 

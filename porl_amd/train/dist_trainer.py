@@ -147,3 +147,9 @@ class DistTrainerBase:
         threshold = self.batch_size if self._online_threshold == "batch" else self.training_learning_step
         return online.run(self, env, policy, num_episodes, max_steps, threshold, self.replay_buffer,
                           self.replay_buffer.push, fast)
+
+    def train_vectorized_dist(self, sim, n_steps, **kw):
+        """act -> step -> learn with the N robots of a DiscreteLidarNavSim and no host synchronisation inside the loop:
+        train/vector_dist.py (`train_vectorized`, the plain-Q loop, keeps turning these trainers away)."""
+        from .vector_dist import train_vectorized_dist
+        return train_vectorized_dist(self, sim, n_steps, **kw)

@@ -20,8 +20,9 @@ and the target network is synchronised after block b when b % update_target_freq
 episode number does).
 
 Plain-Q trainers only: CQLTrainer, DQNTrainer, DDQNTrainer, DDDQNTrainer.  PERTrainer has the same loop around its own
-memory as `train_vectorized_per` (train/vector_per.py, which shares `check_sim`, `check_starts` and `end_of_step` below);
-BCQ and the distributional trainers (C51, QR-DQN, IQN) run in this task through their own `train_online(Env(...))`.
+memory as `train_vectorized_per` (train/vector_per.py), C51Trainer and QRDQNTrainer around their own act and learn calls as
+`train_vectorized_dist` (train/vector_dist.py); both share `check_sim`, `check_starts` and `end_of_step` below.  BCQ and IQN
+run in this task through their own `train_online(Env(...))`.
 """
 from __future__ import annotations
 
@@ -72,14 +73,16 @@ def learn_step(trainer, replay, seed, draw):
     trainer.optimizer.step_count = hp.step
 
 
-def check_sim(eng, sim, n_steps, block, learn_per_step, who):
-    """The argument checks the vectorised loops share (`who` names the loop in the one message that names it)."""
+def check_sim(eng, sim, n_steps, block, learn_per_step, who, n_actions=None):
+    """The argument checks the vectorised loops share (`who` names the loop in the one message that names it).  `n_actions`:
+    the trainer's action count where it is not the network's output count (a distributional head)."""
     S = sim.obs_dim
+    n_actions = eng.cfg.n_actions if n_actions is None else n_actions
     if not sim.auto_reset:
         raise ValueError(f"{who} needs a simulator with auto_reset=True")
-    if S != eng.cfg.state_dim or sim.n_actions != eng.cfg.n_actions:
+    if S != eng.cfg.state_dim or sim.n_actions != n_actions:
         raise ValueError(f"the simulator observes {S} floats and takes {sim.n_actions} actions; the trainer's network maps "
-                         f"{eng.cfg.state_dim} to {eng.cfg.n_actions}")
+                         f"{eng.cfg.state_dim} to {n_actions}")
     if sim.state.device != eng.device:
         raise ValueError(f"simulator on {sim.state.device}, trainer on {eng.device}")
     if n_steps < 1 or block < 1 or learn_per_step < 0:
