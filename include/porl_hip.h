@@ -539,6 +539,8 @@ int porl_qnet_act(porl_qnet* h, int which, const porl_qnet_act_src* src, const p
  *   factor in brackets.  head: Double-DQN choice on the tau''-mean of z_online_next, Bellman targets from z_target_next,
  *   quantile-Huber loss of the taken action's quantiles of z_cur against them; z rows (batch * n, ld); dz (batch * n_cur,
  *   ld) = dL/dz_cur for the batch-mean loss, row_loss (batch), next_actions (batch, optional).
+ * The entry points of the vectorised loop (N robots per step, nothing read back; csrc/iqn_vector.hpp) follow
+ *   porl_iqn_head below, each with its own comment.
  * --------------------------------------------------------------------------------------------- */
 #define PORL_IQN_TENSORS 10
 typedef struct porl_iqn porl_iqn;
@@ -589,6 +591,37 @@ int porl_iqn_head(const float* z_cur, const float* z_online_next, const float* z
                   const int64_t* actions, const float* rewards, const float* dones, const float* taus_prime,
                   int32_t batch, int32_t n_cur, int32_t n_tgt, int32_t n_actions, float gamma, float kappa, float* dz,
                   float* row_loss, int64_t* next_actions, void* stream);
+/* The keyed fraction stream: out[k] = tau(seed, use, draw, first + k) for k < count, where
+ *   tau(seed, use, draw, e) = (float)(sm64(key ^ sm64((draw << 32) | e)) >> 40) * 2^-24,  key = sm64(seed ^ TAG ^ use),
+ * sm64 the mixer of porl_per_sample_keyed's stream and TAG = 0x30C9E7BC03E23535 (csrc/iqn_vector.hpp).  use: 0 acting, 1 tau',
+ * 2 tau''.  Every value is a multiple of 2^-24 in [0, 1).  draw <= 2^32 - 1, 0 <= first, first + count <= 2^32.
+ * Stand-alone: no engine; one launch. */
+int porl_iqn_draw_taus(uint64_t seed, int32_t use, uint64_t draw, int64_t first, int64_t count, float* out, void* stream);
+/* Epsilon-greedy over the quantile values of n robots: z (n * n_tau, ld) fp32, robot i's n_tau rows one after the other,
+ * n_actions values per row (n_actions <= ld <= 128).  q[i, a] = (sum over the rows, ascending, of z[., a]) / n_tau — the
+ * order in which porl_iqn_learn ranks the next state's actions — goes to q (n, n_actions) with row stride q_rs and the
+ * action to out (n) int64, both always, also when the robot explores; the action is porl_qnet_select's rule on those
+ * values, with the same key and draws (seed, env_offset + i, act-step t).  n_tau <= 256, n_actions <= 64, t <= 2^32 - 1.
+ * Stand-alone; one launch, one wave per robot. */
+int porl_iqn_select_rows(const float* z, int64_t ld, int64_t n, int32_t n_tau, int32_t n_actions, double epsilon, uint64_t seed,
+                         uint64_t t, int64_t env_offset, float* q, int64_t q_rs, int64_t* out, void* stream);
+/* Acting for n robots: rows of states (n, row stride s_rs) in chunks of cfg.max_batch — per chunk one staging launch
+ * (states and fractions), the feature layers, the mix, the value layers and porl_iqn_select_rows' kernel on the output rows
+ * where the forward left them: 7 launches.  Robot i's n_tau fractions are taus[i, :] of the caller's dense (n, n_tau)
+ * array, or with taus NULL elements (env_offset + i) * n_tau + j of the acting stream (use 0) at draw t, whatever the
+ * chunking; then (env_offset + n) * n_tau <= 2^32.  n_tau <= cfg.max_tau.  which: 0 online, 1 target.  q, out as
+ * porl_iqn_select_rows'.  Borrows the workspace rows of the learn step's second forward. */
+int porl_iqn_act_rows(porl_iqn* h, int which, const float* states, int64_t s_rs, int64_t n, const float* taus, int32_t n_tau,
+                      double epsilon, uint64_t seed, uint64_t t, int64_t env_offset, float* q, int64_t q_rs, int64_t* out,
+                      void* stream);
+/* porl_iqn_learn on `batch` distinct rows of the first n_rows rows of the replay arrays — the rows
+ * porl_sample_indices(n_rows, batch, seed, draw) writes, drawn inside the gather launch — with tau' (batch, n_cur) and
+ * tau'' (batch, n_tgt) the elements b * n + j of uses 1 and 2 of the fraction stream at draw `draw`, written into the
+ * workspace by one extra launch: bit-equal to porl_sample_indices, two porl_iqn_draw_taus and porl_iqn_learn.
+ * batch <= n_rows <= 2^40, draw <= 2^32 - 1. */
+int porl_iqn_learn_sampled(porl_iqn* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
+                           const float* next_states, int64_t n_rs, const float* dones, int64_t n_rows, int32_t batch,
+                           uint64_t seed, uint64_t draw, int32_t n_cur, int32_t n_tgt, const porl_iqn_hyper* hp, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Building blocks, exported for tests, the replay buffer and other trainers
@@ -1099,7 +1132,7 @@ int porl_qnet_select(const float* q, int64_t q_rs, int32_t n_actions, int64_t n,
                      int64_t env_offset, uint64_t t, int64_t* out, void* stream);
 /* porl_qnet_forward on n rows of states, walked in chunks of the engine's max_batch, into the caller's scratch q (n,
  * n_actions), then porl_qnet_select on it: acting for n robots from one call.  Plain-Q networks only (DQN, Double DQN,
- * Dueling through the composed output layer, CQL); C51 and QR-DQN have porl_qnet_act_rows_dist, IQN is out of scope. */
+ * Dueling through the composed output layer, CQL); C51 and QR-DQN have porl_qnet_act_rows_dist, IQN porl_iqn_act_rows. */
 int porl_qnet_act_rows(porl_qnet* h, int which, const float* states, int64_t s_rs, int64_t n, float* q, int64_t q_rs,
                        double epsilon, uint64_t seed, int64_t env_offset, uint64_t t, int64_t* out, void* stream);
 /* Epsilon-greedy over the outputs of a distributional network: z (n, n_actions * n_sub) fp32 with row stride z_rs, action

@@ -9,6 +9,10 @@
 //   gather | feature layer 0, 1 (three forwards grouped) | mix | value layer 0, 1 (grouped) | head | mean loss |
 //   value.2 wgrad + dgrad | value.0 wgrad + dgrad | Hadamard backward | embedding wgrad | feature.2 wgrad + dgrad |
 //   feature.0 wgrad | clip (3) | Adam                                                                         = 18
+// porl_iqn_learn_sampled is the same body: its gather launch draws the rows (QnetGatherArgs' samp_* fields) and one launch
+// in front of it writes tau' and tau'' from the keyed stream (csrc/iqn_vector.hpp) into the workspace                  = 19
+// Launches of porl_iqn_act_rows, per chunk of max_batch robots (m robots, K fractions each):
+//   staging (states + fractions) | feature layer 0, 1 (M = m) | mix (m * K rows) | value layer 0, 1 | rows head       = 7
 
 namespace {
 
@@ -25,7 +29,9 @@ struct porl_iqn {
   struct {
     int64_t xs, xn, rew, done, actions;          // actions: int64 stored in 2 floats each
     int64_t f0[3], feat[3], emb0, mix[3], hv[3], z[3];
-    int64_t dz, row_loss, dhv, dmix, demb, dfeat, df0, clip, total;
+    int64_t dz, row_loss, dhv, dmix, demb, dfeat, df0, clip;
+    int64_t taup, taupp;                         // fractions drawn on the device: tau' | tau'' and the act path's
+    int64_t total;
   } ws;
   Tune tune = g_tune;
   const void* act_out_host = nullptr;            // porl_iqn_act: last record pointer seen and its device address
@@ -82,6 +88,51 @@ int iqn_launch_mix(const IqnMixArgs& a, hipStream_t s) {
   return PORL_OK;
 }
 
+// draw and element range of the fraction stream: the counter packs (draw, e) as (draw << 32) | e
+int iqn_tau_range_ok(uint64_t draw, int64_t first, int64_t count) {
+  if (draw > (uint64_t)IQN_TAU_MAX_DRAW) PORL_FAIL(PORL_ERR_INVALID, "draw %llu above 2^32 - 1", (unsigned long long)draw);
+  if (first < 0 || first >= IQN_TAU_MAX_ELEMS) PORL_FAIL(PORL_ERR_INVALID, "first %lld outside [0, 2^32)", (long long)first);
+  if (count < 1 || count > IQN_TAU_MAX_ELEMS - first)
+    PORL_FAIL(PORL_ERR_INVALID, "count %lld: elements [%lld, %lld) must be non-empty and end at 2^32", (long long)count, (long long)first, (long long)(first + count));
+  return PORL_OK;
+}
+
+int iqn_launch_taus(const IqnTauArgs& a, int njobs, hipStream_t s) {
+  int64_t most = 0;
+  for (int k = 0; k < njobs; ++k) most = std::max(most, a.job[k].count);
+  hipLaunchKernelGGL(iqn_taus_kernel, dim3((unsigned)((most + 255) / 256), njobs), dim3(256), 0, s, a);
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+// the checks porl_iqn_select_rows and porl_iqn_act_rows share (select_check's rules, in this file's words)
+int iqn_rows_check(int64_t n, int32_t n_tau, int32_t max_tau, int32_t n_actions, double epsilon, uint64_t t, int64_t env_offset,
+                   const float* q, int64_t q_rs, const int64_t* out) {
+  if (!q) PORL_FAIL(PORL_ERR_INVALID, "null q");
+  if (!out) PORL_FAIL(PORL_ERR_INVALID, "null out");
+  if (n < 1 || n > (int64_t(1) << 24)) PORL_FAIL(PORL_ERR_INVALID, "n %lld outside [1, 2^24]", (long long)n);
+  if (n_tau < 1 || n_tau > max_tau) PORL_FAIL(PORL_ERR_INVALID, "n_tau %d outside [1,%d]", n_tau, max_tau);
+  if (n_actions < 1 || n_actions > IQN_MAX_A) PORL_FAIL(PORL_ERR_INVALID, "n_actions %d outside [1,%d]", n_actions, IQN_MAX_A);
+  if (q_rs < n_actions || q_rs > (int64_t(1) << 24)) PORL_FAIL(PORL_ERR_INVALID, "q_rs %lld: a row of action values is %d floats", (long long)q_rs, n_actions);
+  if (!(epsilon >= 0.0 && epsilon <= 1.0)) PORL_FAIL(PORL_ERR_INVALID, "epsilon %g outside [0, 1]", epsilon);
+  if (env_offset < 0 || env_offset > (int64_t(1) << 40)) PORL_FAIL(PORL_ERR_INVALID, "env_offset %lld outside [0, 2^40]", (long long)env_offset);
+  if (t > (uint64_t)IQN_TAU_MAX_DRAW) PORL_FAIL(PORL_ERR_INVALID, "act-step t %llu above 2^32 - 1", (unsigned long long)t);
+  return PORL_OK;
+}
+
+int iqn_launch_rows_head(const float* z, int64_t ld, int64_t n, int32_t n_tau, int32_t n_actions, double epsilon, uint64_t seed,
+                         uint64_t t, int64_t env_offset, float* q, int64_t q_rs, int64_t* out, hipStream_t s) {
+  IqnRowsHeadArgs a{};
+  a.z = z; a.ld = (long long)ld; a.q = q; a.q_rs = (long long)q_rs; a.out = reinterpret_cast<long long*>(out);
+  a.n = (long long)n; a.env_offset = (long long)env_offset; a.t = (long long)t;
+  a.epsilon = epsilon; a.seed = seed; a.K = n_tau; a.A = n_actions;
+  a.vec = aligned16(z) && ld % 4 == 0;
+  ProfScope ps("iqn_rows_head_kernel", s, 0.0, 0.0);
+  hipLaunchKernelGGL(iqn_rows_head_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, a);
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -118,6 +169,7 @@ int porl_iqn_create(const porl_iqn_cfg* c, porl_iqn** out) {
   h->ws.dhv = take(R * h->Hp); h->ws.dmix = take(R * h->Hp); h->ws.demb = take(R * h->Hp);
   h->ws.dfeat = take(B * h->Hp); h->ws.df0 = take(B * h->Hp);
   h->ws.clip = take(2 * CLIP_BLOCKS);                       // CLIP_BLOCKS doubles
+  h->ws.taup = take(R); h->ws.taupp = take(R);
   h->ws.total = o;
   *out = h;
   return PORL_OK;
@@ -173,25 +225,30 @@ int porl_iqn_head(const float* z_cur, const float* z_online_next, const float* z
   return PORL_OK;
 }
 
-int porl_iqn_learn(porl_iqn* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
-                   const float* next_states, int64_t n_rs, const float* dones, const int64_t* idx, int32_t batch,
-                   const float* taus_prime, int32_t n_cur, const float* taus_dprime, int32_t n_tgt, const porl_iqn_hyper* hp,
-                   void* stream) {
+// The learn step on `rows`: idx and the caller's fractions, or — sampled — the keyed draw of rows.samp_n rows inside the
+// gather launch and tau' / tau'' from the fraction stream (uses 1 and 2, draw rows.samp_step) in the workspace.
+static int iqn_learn_rows(porl_iqn* h, const QnetRows& rows, bool sampled, int32_t batch, const float* taus_prime, int32_t n_cur,
+                          const float* taus_dprime, int32_t n_tgt, const porl_iqn_hyper* hp, void* stream) {
   PORL_TRY(iqn_ready(h));
+  const float* states = rows.states; const float* next_states = rows.next_states;
+  const int64_t s_rs = rows.s_rs, n_rs = rows.n_rs;
   if (!hp) PORL_FAIL(PORL_ERR_INVALID, "null hp");
   if (!states) PORL_FAIL(PORL_ERR_INVALID, "null states");
-  if (!actions) PORL_FAIL(PORL_ERR_INVALID, "null actions");
-  if (!rewards) PORL_FAIL(PORL_ERR_INVALID, "null rewards");
+  if (!rows.actions) PORL_FAIL(PORL_ERR_INVALID, "null actions");
+  if (!rows.rewards) PORL_FAIL(PORL_ERR_INVALID, "null rewards");
   if (!next_states) PORL_FAIL(PORL_ERR_INVALID, "null next_states");
-  if (!dones) PORL_FAIL(PORL_ERR_INVALID, "null dones");
-  if (!taus_prime) PORL_FAIL(PORL_ERR_INVALID, "null taus_prime");
-  if (!taus_dprime) PORL_FAIL(PORL_ERR_INVALID, "null taus_dprime");
+  if (!rows.dones) PORL_FAIL(PORL_ERR_INVALID, "null dones");
+  if (!sampled && !taus_prime) PORL_FAIL(PORL_ERR_INVALID, "null taus_prime");
+  if (!sampled && !taus_dprime) PORL_FAIL(PORL_ERR_INVALID, "null taus_dprime");
   const porl_iqn_cfg& c = h->cfg;
   if (batch < 1 || batch > c.max_batch) PORL_FAIL(PORL_ERR_INVALID, "batch %d outside [1,%d]", batch, c.max_batch);
+  if (sampled && (rows.samp_n < batch || rows.samp_n > (int64_t(1) << 40)))
+    PORL_FAIL(PORL_ERR_INVALID, "n_rows %lld: need batch %d <= n_rows <= 2^40", (long long)rows.samp_n, batch);
   if (s_rs < c.state_dim) PORL_FAIL(PORL_ERR_INVALID, "s_rs %lld below state_dim %d", (long long)s_rs, c.state_dim);
   if (n_rs < c.state_dim) PORL_FAIL(PORL_ERR_INVALID, "n_rs %lld below state_dim %d", (long long)n_rs, c.state_dim);
   if (n_cur < 1 || n_cur > c.max_tau) PORL_FAIL(PORL_ERR_INVALID, "n_cur %d outside [1,%d]", n_cur, c.max_tau);
   if (n_tgt < 1 || n_tgt > c.max_tau) PORL_FAIL(PORL_ERR_INVALID, "n_tgt %d outside [1,%d]", n_tgt, c.max_tau);
+  if (sampled) PORL_TRY(iqn_tau_range_ok(rows.samp_step, 0, (int64_t)batch * std::max(n_cur, n_tgt)));
   if (hp->step < 1) PORL_FAIL(PORL_ERR_INVALID, "step %d: adam step must be >= 1", hp->step);
   if (!(hp->max_norm > 0.f)) PORL_FAIL(PORL_ERR_INVALID, "max_norm must be positive");
   DevGuard _dg(h->device);
@@ -199,13 +256,24 @@ int porl_iqn_learn(porl_iqn* h, const float* states, int64_t s_rs, const int64_t
   float* W = h->buf.workspace;
   const int B = batch, S = c.state_dim, H = c.hidden, E = c.embedding_dim, A = c.n_actions;
   const int Sp = h->Sp, Hp = h->Hp, Ap = h->Ap;
+  if (sampled) {
+    IqnTauArgs a{};
+    a.job[0] = IqnTauJob{W + h->ws.taup, iqn_tau_key(rows.samp_seed, 1), rows.samp_step, 0, (int64_t)B * n_cur};
+    a.job[1] = IqnTauJob{W + h->ws.taupp, iqn_tau_key(rows.samp_seed, 2), rows.samp_step, 0, (int64_t)B * n_tgt};
+    PORL_TRY(iqn_launch_taus(a, 2, s));
+    taus_prime = W + h->ws.taup; taus_dprime = W + h->ws.taupp;
+  }
   {
     QnetGatherArgs a{};
     a.states = states; a.next_states = next_states; a.s_rs = (long)s_rs; a.n_rs = (long)n_rs;
-    a.actions = actions; a.rew = rewards; a.done = dones; a.idx = idx;
+    a.actions = rows.actions; a.rew = rows.rewards; a.done = rows.dones; a.idx = rows.idx;
     a.xs = W + h->ws.xs; a.xn = W + h->ws.xn; a.act_out = reinterpret_cast<int64_t*>(W + h->ws.actions);
     a.rew_out = W + h->ws.rew; a.done_out = W + h->ws.done;
     a.B = B; a.S = S; a.ld = Sp;
+    if (sampled) {
+      a.samp_n = rows.samp_n; a.samp_seed = rows.samp_seed; a.samp_step = rows.samp_step; a.samp_hb = feistel_half_bits(rows.samp_n);
+      a.idx = nullptr;
+    }
     hipLaunchKernelGGL(qnet_gather_kernel, dim3((unsigned)(((long)B * Sp + 255) / 256)), dim3(256), 0, s, a);
     PORL_HIP(hipGetLastError());
   }
@@ -272,6 +340,91 @@ int porl_iqn_learn(porl_iqn* h, const float* states, int64_t s_rs, const int64_t
   }
   return adam_launch(h->buf.params, h->buf.grads, h->buf.adam_m, h->buf.adam_v, nullptr, c.n_params, hp->lr, hp->step,
                      hp->adam_beta1, hp->adam_beta2, hp->adam_eps, 0.0, s);
+}
+
+int porl_iqn_learn(porl_iqn* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
+                   const float* next_states, int64_t n_rs, const float* dones, const int64_t* idx, int32_t batch,
+                   const float* taus_prime, int32_t n_cur, const float* taus_dprime, int32_t n_tgt, const porl_iqn_hyper* hp,
+                   void* stream) {
+  const QnetRows rows{states, s_rs, actions, rewards, next_states, n_rs, dones, idx};
+  return iqn_learn_rows(h, rows, false, batch, taus_prime, n_cur, taus_dprime, n_tgt, hp, stream);
+}
+
+int porl_iqn_learn_sampled(porl_iqn* h, const float* states, int64_t s_rs, const int64_t* actions, const float* rewards,
+                           const float* next_states, int64_t n_rs, const float* dones, int64_t n_rows, int32_t batch,
+                           uint64_t seed, uint64_t draw, int32_t n_cur, int32_t n_tgt, const porl_iqn_hyper* hp, void* stream) {
+  const QnetRows rows{states, s_rs, actions, rewards, next_states, n_rs, dones, nullptr, n_rows, seed, draw};
+  return iqn_learn_rows(h, rows, true, batch, nullptr, n_cur, nullptr, n_tgt, hp, stream);
+}
+
+int porl_iqn_draw_taus(uint64_t seed, int32_t use, uint64_t draw, int64_t first, int64_t count, float* out, void* stream) {
+  if (!out) PORL_FAIL(PORL_ERR_INVALID, "null out");
+  if (use < 0 || use > 2) PORL_FAIL(PORL_ERR_INVALID, "use %d: 0 acting, 1 tau', 2 tau''", use);
+  PORL_TRY(iqn_tau_range_ok(draw, first, count));
+  DevGuard _dg(device_of(out));
+  IqnTauArgs a{};
+  a.job[0] = IqnTauJob{out, iqn_tau_key(seed, use), draw, first, count};
+  return iqn_launch_taus(a, 1, (hipStream_t)stream);
+}
+
+int porl_iqn_select_rows(const float* z, int64_t ld, int64_t n, int32_t n_tau, int32_t n_actions, double epsilon, uint64_t seed,
+                         uint64_t t, int64_t env_offset, float* q, int64_t q_rs, int64_t* out, void* stream) {
+  if (!z) PORL_FAIL(PORL_ERR_INVALID, "null z");
+  PORL_TRY(iqn_rows_check(n, n_tau, IQN_MAX_TAU, n_actions, epsilon, t, env_offset, q, q_rs, out));
+  if (ld < n_actions || ld > IQN_ROWS_MAX_LD) PORL_FAIL(PORL_ERR_INVALID, "ld %lld outside [n_actions %d, %d]", (long long)ld, n_actions, IQN_ROWS_MAX_LD);
+  DevGuard _dg(device_of(out));
+  return iqn_launch_rows_head(z, ld, n, n_tau, n_actions, epsilon, seed, t, env_offset, q, q_rs, out, (hipStream_t)stream);
+}
+
+// chunks of max_batch robots, each through the rows of forward 1 (a learn step on the same stream has finished with them)
+int porl_iqn_act_rows(porl_iqn* h, int which, const float* states, int64_t s_rs, int64_t n, const float* taus, int32_t n_tau,
+                      double epsilon, uint64_t seed, uint64_t t, int64_t env_offset, float* q, int64_t q_rs, int64_t* out,
+                      void* stream) {
+  PORL_TRY(iqn_ready(h));
+  if (which != 0 && which != 1) PORL_FAIL(PORL_ERR_INVALID, "which %d: 0 online, 1 target", which);
+  if (!states) PORL_FAIL(PORL_ERR_INVALID, "null states");
+  const porl_iqn_cfg& c = h->cfg;
+  PORL_TRY(iqn_rows_check(n, n_tau, c.max_tau, c.n_actions, epsilon, t, env_offset, q, q_rs, out));
+  if (s_rs < c.state_dim || s_rs > (int64_t(1) << 24)) PORL_FAIL(PORL_ERR_INVALID, "s_rs %lld below state_dim %d or above 2^24", (long long)s_rs, c.state_dim);
+  if (!taus && (env_offset + n) * n_tau > IQN_TAU_MAX_ELEMS)
+    PORL_FAIL(PORL_ERR_INVALID, "(env_offset %lld + n %lld) x n_tau %d: the fraction stream numbers elements below 2^32", (long long)env_offset, (long long)n, n_tau);
+  DevGuard _dg(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  float* W = h->buf.workspace;
+  const float* P = which ? h->buf.params_tgt : h->buf.params;
+  const int S = c.state_dim, H = c.hidden, E = c.embedding_dim, A = c.n_actions, K = n_tau;
+  const int Sp = h->Sp, Hp = h->Hp, Ap = h->Ap;
+  float* x = W + h->ws.xn; float* tau = W + h->ws.taupp;
+  float* f0 = W + h->ws.f0[1]; float* feat = W + h->ws.feat[1]; float* mix = W + h->ws.mix[1]; float* hv = W + h->ws.hv[1];
+  float* z = W + h->ws.z[1];
+  const float* par[1] = {P};
+  const uint64_t key = iqn_tau_key(seed, 0);
+  for (int64_t r = 0; r < n; r += c.max_batch) {
+    const int m = (int)std::min<int64_t>(c.max_batch, n - r);
+    {
+      IqnStageArgs a{};
+      a.states = states + r * s_rs; a.s_rs = (long long)s_rs; a.xs = x;
+      a.taus = taus ? taus + r * K : nullptr; a.taus_out = tau;
+      a.key = key; a.t = t; a.first_e = (long long)((env_offset + r) * K);
+      a.m = m; a.S = S; a.Sp = Sp; a.K = K;
+      const long groups = std::max((long)m * (Sp / 4), ((long)m * K + 3) / 4);
+      hipLaunchKernelGGL(iqn_act_stage_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, a);
+      PORL_HIP(hipGetLastError());
+    }
+    const int Mb[1] = {m}, Mr[1] = {m * K};
+    { const float* in[1] = {x}; float* o[1] = {f0}; PORL_TRY(iqn_fwd_layer(h, 1, in, Sp, Mb, par, IQN_F0W, o, Hp, H, S, ACT_RELU, s)); }
+    { const float* in[1] = {f0}; float* o[1] = {feat}; PORL_TRY(iqn_fwd_layer(h, 1, in, Hp, Mb, par, IQN_F1W, o, Hp, H, H, ACT_RELU, s)); }
+    {
+      IqnMixArgs a{};
+      a.nprob = 1; a.E = E; a.H = H;
+      a.p[0] = IqnMixProb{feat, (long)Hp, tau, P + c.offset[IQN_QEW], (long)E, P + c.offset[IQN_QEB], mix, (long)Hp, nullptr, m * K, K};
+      PORL_TRY(iqn_launch_mix(a, s));
+    }
+    { const float* in[1] = {mix}; float* o[1] = {hv}; PORL_TRY(iqn_fwd_layer(h, 1, in, Hp, Mr, par, IQN_V0W, o, Hp, H, H, ACT_RELU, s)); }
+    { const float* in[1] = {hv}; float* o[1] = {z}; PORL_TRY(iqn_fwd_layer(h, 1, in, Hp, Mr, par, IQN_V1W, o, Ap, A, H, ACT_NONE, s)); }
+    PORL_TRY(iqn_launch_rows_head(z, Ap, m, K, A, epsilon, seed, t, env_offset + r, q + r * q_rs, q_rs, out + r, s));
+  }
+  return PORL_OK;
 }
 
 int porl_iqn_act(porl_iqn* h, int which, const porl_qnet_act_src* src, const float* taus, int32_t n_tau, int32_t n_stats,

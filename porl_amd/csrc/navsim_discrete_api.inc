@@ -5,7 +5,7 @@
 //
 // porl_qnet_act_rows covers the plain-Q epilogue — DQN, Double DQN, Dueling (through the composed output layer) and CQL;
 // porl_qnet_act_rows_dist the distributional heads on the same engine (C51, QR-DQN), whose n x A*NS outputs stay in the
-// workspace.  IQN is out of scope here: its trainer acts through porl_iqn_act.
+// workspace.  IQN has its own engine: porl_iqn_act_rows (csrc/iqn_api.inc).
 
 namespace {
 

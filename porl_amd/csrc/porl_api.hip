@@ -32,6 +32,7 @@
 #include "navsim.hpp"
 #include "navsim_discrete.hpp"
 #include "dist_act.hpp"
+#include "iqn_vector.hpp"
 
 using namespace porl;
 

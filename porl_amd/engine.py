@@ -923,6 +923,42 @@ class IqnEngine:
                                        C.c_void_p(out.data_ptr()), N.current_stream_ptr(self.device)), "porl_iqn_act")
         return out
 
+    def act_rows(self, states, n_tau, epsilon, seed, t, env_offset=0, taus=None, q=None, out=None, which=0):
+        """Epsilon-greedy actions (n,) int64 on the device for the n rows of `states` (porl_iqn_act_rows): the forward in
+        chunks of max_batch under `n_tau` fractions per robot — `taus` (n, n_tau), or with None the elements
+        (env_offset + i) * n_tau + j of the acting stream at draw `t` (iqn_draw_taus, use 0) — then iqn_select_rows' kernel
+        on each chunk's output rows in the workspace.  `q` (n, A) receives the action values; nothing is read back."""
+        if not self._bound:
+            raise N.NativeError("porl_iqn_act_rows: the engine is not bound")
+        x = states
+        if x.dim() != 2 or x.dtype != torch.float32 or x.device != self.device or x.shape[1] != self.cfg.state_dim or \
+                (x.shape[1] > 1 and x.stride(1) != 1):
+            raise RuntimeError(f"states: need (n, {self.cfg.state_dim}) float32 rows with unit column stride on {self.device}")
+        n, A = x.shape[0], self.cfg.n_actions
+        if taus is not None and (taus.dtype != torch.float32 or taus.device != self.device or not taus.is_contiguous() or
+                                 tuple(taus.shape) != (n, int(n_tau))):
+            raise RuntimeError(f"taus: need a contiguous ({n}, {int(n_tau)}) float32 tensor on {self.device}")
+        if q is None:
+            q = torch.empty(n, A, dtype=torch.float32, device=self.device)
+        if q.dim() != 2 or q.shape != (n, A) or q.device != self.device:
+            raise RuntimeError(f"q: expected ({n}, {A}) on {self.device}, got {tuple(q.shape)} on {q.device}")
+        out, q_rs = _select_args(q, out)
+        s_rs = x.stride(0) if n > 1 else max(x.stride(0), x.shape[1])
+        N.check(self._lib.porl_iqn_act_rows(self._h, int(which), N.ptr(x), s_rs, n, N.ptr(taus), int(n_tau), float(epsilon),
+                                            int(seed) & (2 ** 64 - 1), int(t), int(env_offset), N.ptr(q), q_rs, N.ptr(out),
+                                            N.current_stream_ptr(self.device)), "porl_iqn_act_rows")
+        return out
+
+    def learn_sampled(self, hp, states, actions, rewards, next_states, dones, n_rows, batch, seed, draw, n_cur, n_tgt):
+        """learn on the rows engine.sample_indices(n_rows, batch, seed, draw) would give, drawn inside the gather launch, with
+        tau' (batch, n_cur) and tau'' (batch, n_tgt) from the fraction stream (iqn_draw_taus, uses 1 and 2, draw `draw`)
+        (porl_iqn_learn_sampled); the statistics land in stats[0:3]."""
+        args = replay_args(states, actions, rewards, next_states, dones, self.cfg.state_dim, self.device, n_rows=n_rows)
+        N.check(self._lib.porl_iqn_learn_sampled(self._h, *args, int(n_rows), int(batch), int(seed) & (2 ** 64 - 1), int(draw),
+                                                 int(n_cur), int(n_tgt), C.byref(hp), N.current_stream_ptr(self.device)),
+                "porl_iqn_learn_sampled")
+        return batch
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):
@@ -1037,6 +1073,41 @@ def dist_select(z, head, epsilon, seed, t, env_offset=0, q=None, out=None):
     z_rs = z.stride(0) if n > 1 else max(z.stride(0), w)
     N.check(N.lib().porl_dist_select(N.ptr(z), z_rs, C.byref(head), n, N.ptr(q), q_rs, float(epsilon), int(seed) & (2 ** 64 - 1),
                                      int(env_offset), int(t), N.ptr(out), N.current_stream_ptr(z)), "porl_dist_select")
+    return out
+
+
+def iqn_draw_taus(seed, use, draw, first, count, out=None, device="cuda"):
+    """Elements [first, first + count) of the keyed fraction stream (float32, on the device; porl_iqn_draw_taus):
+    use 0 the acting fractions, 1 tau', 2 tau''.  Every value is a multiple of 2^-24 in [0, 1)."""
+    if out is None:
+        out = torch.empty(max(int(count), 0), dtype=torch.float32, device=device)
+    elif out.dtype != torch.float32 or out.numel() != count or not out.is_contiguous():
+        raise RuntimeError(f"out: need {count} contiguous float32")
+    N.check(N.lib().porl_iqn_draw_taus(int(seed) & (2 ** 64 - 1), int(use), int(draw), int(first), int(count), N.ptr(out),
+                                       N.current_stream_ptr(out)), "porl_iqn_draw_taus")
+    return out
+
+
+def iqn_select_rows(z, n_tau, epsilon, seed, t, env_offset=0, q=None, out=None):
+    """Epsilon-greedy actions (n,) int64 on the device from the quantile values z (n * n_tau, A) of n robots, robot i's
+    n_tau rows one after the other (a column slice of a wider table is fine; porl_iqn_select_rows): the mean over a
+    robot's rows, summed in the order the learn step ranks the next state's actions by, written to `q` (n, A) when given,
+    then qnet_select's rule on it with the same key and draws; nothing is read back."""
+    if z.dim() != 2 or z.dtype != torch.float32 or z.device.type != "cuda" or (z.shape[1] > 1 and z.stride(1) != 1):
+        raise RuntimeError("z: need a (n * n_tau, n_actions) float32 table with unit column stride on a HIP device")
+    n_tau = int(n_tau)
+    if n_tau < 1 or z.shape[0] % n_tau:
+        raise RuntimeError(f"z: {z.shape[0]} rows are not a multiple of n_tau {n_tau}")
+    n, A = z.shape[0] // n_tau, z.shape[1]
+    if q is None:
+        q = torch.empty(n, max(A, 1), dtype=torch.float32, device=z.device)
+    if q.dim() != 2 or q.shape != (n, A) or q.device != z.device:
+        raise RuntimeError(f"q: expected ({n}, {A}) on {z.device}, got {tuple(q.shape)} on {q.device}")
+    out, q_rs = _select_args(q, out)
+    ld = z.stride(0) if z.shape[0] > 1 else max(z.stride(0), A)
+    N.check(N.lib().porl_iqn_select_rows(N.ptr(z), ld, n, n_tau, A, float(epsilon), int(seed) & (2 ** 64 - 1), int(t),
+                                         int(env_offset), N.ptr(q), q_rs, N.ptr(out), N.current_stream_ptr(z)),
+            "porl_iqn_select_rows")
     return out
 
 

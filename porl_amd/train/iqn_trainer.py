@@ -22,7 +22,8 @@ parameters, gradients and Adam moments live in one flat buffer each (clip and Ad
 `learn_indexed` / `act_greedy` are the same step and the same greedy action from ONE native call each (engine.IqnEngine,
 csrc/iqn_api.inc) on rows of the replay mirror: no autograd, no intermediate torch tensor, no host synchronisation inside
 the step.  The engine binds to the flat buffers above, so both paths share one state and may be interleaved.
-`train_online` runs on them (train/online.py:_FastIQN) when nothing the loop calls has been overridden.
+`train_online` runs on them (train/online.py:_FastIQN) when nothing the loop calls has been overridden;
+`train_vectorized_iqn` (train/vector_iqn.py) runs the same engine with N robots per step.
 """
 from __future__ import annotations
 
@@ -288,3 +289,9 @@ class IQNTrainer:
         fast = online._FastIQN(self) if online.fast_iqn_ok(self) else None
         return online.run(self, env, policy, num_episodes, max_steps, self.training_learning_step, self.replay_buffer,
                           self.replay_buffer.push, fast=fast)
+
+    def train_vectorized_iqn(self, sim, n_steps, **kw):
+        """act -> step -> learn with the N robots of a DiscreteLidarNavSim and no host synchronisation inside the loop:
+        train/vector_iqn.py (`train_vectorized`, the plain-Q loop, keeps turning this trainer away)."""
+        from .vector_iqn import train_vectorized_iqn
+        return train_vectorized_iqn(self, sim, n_steps, **kw)

@@ -19,8 +19,8 @@ trainer so a second call continues the first, and nothing is read back before th
 training_learning_step for QR-DQN (dqn_trainer.py:148).
 
 `train_vectorized(qr, ...)` still refuses a distributional trainer (its message is pinned by a test); the entry points can be
-folded once that test may move.  IQN has its own engine and BCQ is offline: both stay with
-`train_online(Env(...))`.
+folded once that test may move.  IQN has its own engine and its own loop, `train_vectorized_iqn`
+(train/vector_iqn.py); BCQ is offline.
 """
 from __future__ import annotations
 

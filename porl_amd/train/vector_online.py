@@ -21,8 +21,8 @@ episode number does).
 
 Plain-Q trainers only: CQLTrainer, DQNTrainer, DDQNTrainer, DDDQNTrainer.  PERTrainer has the same loop around its own
 memory as `train_vectorized_per` (train/vector_per.py), C51Trainer and QRDQNTrainer around their own act and learn calls as
-`train_vectorized_dist` (train/vector_dist.py); both share `check_sim`, `check_starts` and `end_of_step` below.  BCQ and IQN
-run in this task through their own `train_online(Env(...))`.
+`train_vectorized_dist` (train/vector_dist.py), IQNTrainer on its own engine as `train_vectorized_iqn`
+(train/vector_iqn.py); all three share `check_sim`, `check_starts` and `end_of_step` below.  BCQ is offline.
 """
 from __future__ import annotations
 
