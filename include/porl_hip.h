@@ -1151,6 +1151,28 @@ int porl_dist_select(const float* z, int64_t z_rs, const porl_dist_head* head, i
 int porl_qnet_act_rows_dist(porl_qnet* h, int which, const float* states, int64_t s_rs, int64_t n, const porl_dist_head* head,
                             float* q, int64_t q_rs, double epsilon, uint64_t seed, int64_t env_offset, uint64_t t,
                             int64_t* out, void* stream);
+/* Epsilon-greedy under discrete BCQ's constraint (bcq.py:59-72), for n robots in one launch: q (n, n_actions) fp32 action
+ * values with row stride q_rs, logits (n, n_actions) fp32 outputs of the behaviour network with row stride z_rs,
+ * n_actions <= 64.  Per robot: p = softmax(logits) in porl_softmax_mask's order and expressions (the same bits);
+ * allowed_j = p_j > threshold (absolute, finite and in [0, 1]); mask (NULL: none), dense (n, n_actions) fp32, receives the
+ * 0 / 1 row, also when the robot explores.  Exploration is porl_qnet_select's — the same key and draws, u1 < epsilon:
+ * floor(n_actions * u2) over ALL actions, as the reference explores.  Otherwise the arg-max of v_j = q_j + (mask_j - 1) *
+ * 1e10f in fp32 — the expression porl_qnet_bcq_learn's step kernel ranks the next state's actions by — first maximum, a
+ * NaN in v counting as the maximum.  A row with every action masked is ranked by the same v_j (action 0 when every
+ * |q_j| < 512).  With threshold 0 and finite logits in [-20, 20] every action is allowed and the result is
+ * porl_qnet_select's.  Stateless; nothing is read back; every argument is checked before the launch. */
+int porl_bcq_select(const float* q, int64_t q_rs, const float* logits, int64_t z_rs, int32_t n_actions, int64_t n,
+                    float threshold, double epsilon, uint64_t seed, int64_t env_offset, uint64_t t, float* mask, int64_t* out,
+                    void* stream);
+/* porl_qnet_act_rows under the constraint: n rows of states walked in chunks of the smaller max_batch of the two engines,
+ * porl_qnet_forward of h (parameters `which`) into the caller's q (n, n_actions) and of beh (its online parameters) into
+ * the caller's logits (n, n_actions), then ONE launch of porl_bcq_select's kernel for all n.  As porl_qnet_forward
+ * writes them, a row of q and of logits is written over its whole stride (zeros behind the n_actions values): n * q_rs
+ * and n * z_rs floats must be writable.  The two engines must be bound, distinct, on one device and agree in state_dim
+ * and n_actions. */
+int porl_qnet_act_rows_bcq(porl_qnet* h, porl_qnet* beh, int which, const float* states, int64_t s_rs, int64_t n, float* q,
+                           int64_t q_rs, float* logits, int64_t z_rs, float threshold, double epsilon, uint64_t seed,
+                           int64_t env_offset, uint64_t t, float* mask, int64_t* out, void* stream);
 
 /* Experiment knobs (scheduling only, never the mathematics).  "gemm_lds_pad": extra dynamic LDS bytes per GEMM block,
  * limiting how many blocks share a CU.  "qnet_fused": 0 forces the multi-launch CQL path.  porl_tune_set sets the process

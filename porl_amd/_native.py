@@ -47,6 +47,7 @@ SYMBOLS = [
     "porl_nav_dreset", "porl_nav_dstep", "porl_qnet_select", "porl_qnet_act_rows",
     "porl_dist_select", "porl_qnet_act_rows_dist", "porl_qnet_dist_learn_sampled",
     "porl_iqn_draw_taus", "porl_iqn_select_rows", "porl_iqn_act_rows", "porl_iqn_learn_sampled",
+    "porl_bcq_select", "porl_qnet_act_rows_bcq",
 ]
 
 
@@ -345,6 +346,9 @@ def _declare(lib):
     lib.porl_iqn_act_rows.argtypes = [vp, C.c_int, vp, i64, i64, vp, i32, f64, C.c_uint64, C.c_uint64, i64, vp, i64, vp, vp]
     lib.porl_iqn_learn_sampled.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, i64, i32, C.c_uint64, C.c_uint64, i32, i32,
                                            C.POINTER(IqnHyper), vp]
+    lib.porl_bcq_select.argtypes = [vp, i64, vp, i64, i32, i64, f32, f64, C.c_uint64, i64, C.c_uint64, vp, vp, vp]
+    lib.porl_qnet_act_rows_bcq.argtypes = [vp, vp, C.c_int, vp, i64, i64, vp, i64, vp, i64, f32, f64, C.c_uint64, i64,
+                                           C.c_uint64, vp, vp, vp]
     lib.porl_prof_enable.argtypes = [C.c_int]
     lib.porl_prof_read.argtypes = [C.POINTER(ProfEntry), C.c_int]
     for name in SYMBOLS:

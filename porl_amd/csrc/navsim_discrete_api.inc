@@ -5,7 +5,8 @@
 //
 // porl_qnet_act_rows covers the plain-Q epilogue — DQN, Double DQN, Dueling (through the composed output layer) and CQL;
 // porl_qnet_act_rows_dist the distributional heads on the same engine (C51, QR-DQN), whose n x A*NS outputs stay in the
-// workspace.  IQN has its own engine: porl_iqn_act_rows (csrc/iqn_api.inc).
+// workspace.  IQN has its own engine: porl_iqn_act_rows (csrc/iqn_api.inc).  porl_bcq_select and porl_qnet_act_rows_bcq are
+// discrete BCQ's constrained rule on two engines (csrc/bcq_act.hpp).
 
 namespace {
 
@@ -75,6 +76,28 @@ int dist_select_launch(const float* z, int64_t z_rs, const porl_dist_head* head,
   a.epsilon = epsilon; a.seed = seed;
   a.kind = head->kind == PORL_DIST_QR ? 0 : 1; a.A = head->n_actions; a.NS = head->n_sub;
   hipLaunchKernelGGL(dist_select_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, a);
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+
+// select_check's rules, then the behaviour logits, the threshold and the optional mask of the BCQ-constrained rule
+int bcq_select_check(const float* q, int64_t q_rs, const float* logits, int64_t z_rs, int32_t n_actions, int64_t n,
+                     float threshold, double epsilon, int64_t env_offset, uint64_t t, const float* mask, const int64_t* out) {
+  PORL_TRY(select_check(q, q_rs, n_actions, n, epsilon, env_offset, t, out));
+  if (!logits) PORL_FAIL(PORL_ERR_INVALID, "null behaviour logits");
+  if (z_rs < n_actions || z_rs > NAV_MAX_STRIDE)
+    PORL_FAIL(PORL_ERR_INVALID, "z_rs %lld: a row of behaviour logits is %d floats", (long long)z_rs, n_actions);
+  if (!std::isfinite(threshold) || threshold < 0.f || threshold > 1.f) PORL_FAIL(PORL_ERR_INVALID, "threshold must lie in [0, 1]");
+  if (mask && (mask == q || mask == logits)) PORL_FAIL(PORL_ERR_INVALID, "mask must not be q or logits");
+  return PORL_OK;
+}
+
+int bcq_select_launch(const float* q, int64_t q_rs, const float* logits, int64_t z_rs, int32_t n_actions, int64_t n,
+                      float threshold, double epsilon, uint64_t seed, int64_t env_offset, uint64_t t, float* mask, int64_t* out,
+                      hipStream_t s) {
+  hipLaunchKernelGGL(bcq_select_kernel, dim3((unsigned)((n + SELECT_THREADS - 1) / SELECT_THREADS)), dim3(SELECT_THREADS), 0, s, q,
+                     (long long)q_rs, logits, (long long)z_rs, (int)n_actions, (long long)n, threshold, epsilon, seed,
+                     (long long)env_offset, (long long)t, mask, reinterpret_cast<long long*>(out));
   PORL_HIP(hipGetLastError());
   return PORL_OK;
 }
@@ -211,6 +234,43 @@ int porl_qnet_act_rows_dist(porl_qnet* h, int which, const float* states, int64_
     PORL_TRY(dist_select_launch(z, h->ld[L], head, nb, q + r * q_rs, q_rs, epsilon, seed, env_offset + r, t, out + r, s));
   }
   return PORL_OK;
+}
+
+int porl_bcq_select(const float* q, int64_t q_rs, const float* logits, int64_t z_rs, int32_t n_actions, int64_t n,
+                    float threshold, double epsilon, uint64_t seed, int64_t env_offset, uint64_t t, float* mask, int64_t* out,
+                    void* stream) {
+  PORL_TRY(bcq_select_check(q, q_rs, logits, z_rs, n_actions, n, threshold, epsilon, env_offset, t, mask, out));
+  DevGuard _dg(device_of(out));
+  return bcq_select_launch(q, q_rs, logits, z_rs, n_actions, n, threshold, epsilon, seed, env_offset, t, mask, out,
+                           (hipStream_t)stream);
+}
+
+// chunks of the smaller max_batch: the Q engine's forward into q, the behaviour engine's into logits; one select launch
+int porl_qnet_act_rows_bcq(porl_qnet* h, porl_qnet* beh, int which, const float* states, int64_t s_rs, int64_t n, float* q,
+                           int64_t q_rs, float* logits, int64_t z_rs, float threshold, double epsilon, uint64_t seed,
+                           int64_t env_offset, uint64_t t, float* mask, int64_t* out, void* stream) {
+  PORL_TRY(qnet_ready(h, false));
+  PORL_TRY(qnet_ready(beh, false));
+  if (which != 0 && which != 1) PORL_FAIL(PORL_ERR_INVALID, "which %d: 0 online, 1 target", which);
+  if (beh == h) PORL_FAIL(PORL_ERR_INVALID, "the behaviour engine must not be the Q engine");
+  if (beh->device != h->device) PORL_FAIL(PORL_ERR_INVALID, "the two engines live on different devices");
+  if (beh->cfg.state_dim != h->cfg.state_dim || beh->cfg.n_actions != h->cfg.n_actions)
+    PORL_FAIL(PORL_ERR_INVALID, "behaviour network (%d -> %d) does not match the Q network (%d -> %d)", beh->cfg.state_dim,
+              beh->cfg.n_actions, h->cfg.state_dim, h->cfg.n_actions);
+  if (!states) PORL_FAIL(PORL_ERR_INVALID, "null states");
+  if (s_rs < h->cfg.state_dim || s_rs > NAV_MAX_STRIDE)
+    PORL_FAIL(PORL_ERR_INVALID, "s_rs %lld: a state is %d floats", (long long)s_rs, h->cfg.state_dim);
+  PORL_TRY(bcq_select_check(q, q_rs, logits, z_rs, h->cfg.n_actions, n, threshold, epsilon, env_offset, t, mask, out));
+  if (q == logits) PORL_FAIL(PORL_ERR_INVALID, "q and logits must be two tables");
+  DevGuard _dg(h->device);
+  const int64_t mb = std::min(h->cfg.max_batch, beh->cfg.max_batch);
+  for (int64_t r = 0; r < n; r += mb) {
+    const int32_t nb = (int32_t)std::min(mb, n - r);
+    PORL_TRY(porl_qnet_forward(h, which, states + r * s_rs, s_rs, nb, q + r * q_rs, q_rs, stream));
+    PORL_TRY(porl_qnet_forward(beh, 0, states + r * s_rs, s_rs, nb, logits + r * z_rs, z_rs, stream));
+  }
+  return bcq_select_launch(q, q_rs, logits, z_rs, h->cfg.n_actions, n, threshold, epsilon, seed, env_offset, t, mask, out,
+                           (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -33,6 +33,7 @@
 #include "navsim_discrete.hpp"
 #include "dist_act.hpp"
 #include "iqn_vector.hpp"
+#include "bcq_act.hpp"
 
 using namespace porl;
 

@@ -820,6 +820,32 @@ class QnetEngine:
                                                   N.current_stream_ptr(self.device)), "porl_qnet_act_rows_dist")
         return out
 
+    def act_rows_bcq(self, beh_engine, states, threshold, epsilon, seed, t, env_offset=0, q=None, logits=None, mask=None,
+                     out=None, which=0):
+        """act_rows under discrete BCQ's constraint (porl_qnet_act_rows_bcq; `self` holds the Q-networks, `beh_engine` the
+        behaviour policy): both forwards in chunks of the smaller max_batch into the scratch `q` and `logits` (n, A, dense),
+        then bcq_select's kernel once for all n rows.  `mask` (n, A), optional, receives the 0 / 1 rows."""
+        self._ensure_bound()
+        beh_engine._ensure_bound()
+        x = self._states(states)
+        n, A = x.shape[0], self.cfg.n_actions
+        if q is None:
+            q = torch.empty(n, A, dtype=torch.float32, device=self.device)
+        if logits is None:
+            logits = torch.empty(n, A, dtype=torch.float32, device=self.device)
+        for name, tab in (("q", q), ("logits", logits)):
+            # dense: porl_qnet_forward writes a row over its whole stride, zeros behind the A values
+            if tab.shape != (n, A) or tab.device != self.device or tab.dtype != torch.float32 or not tab.is_contiguous():
+                raise RuntimeError(f"{name}: expected a contiguous ({n}, {A}) float32 table on {self.device}, got "
+                                   f"{tuple(tab.shape)} on {tab.device}")
+        out, q_rs, z_rs, mask = _bcq_select_args(q, logits, mask, out)
+        N.check(self._lib.porl_qnet_act_rows_bcq(self._h, beh_engine._h, int(which), N.ptr(x),
+                                                 x.stride(0) if n > 1 else max(x.stride(0), x.shape[1]), n, N.ptr(q), q_rs,
+                                                 N.ptr(logits), z_rs, float(threshold), float(epsilon), int(seed) & (2 ** 64 - 1),
+                                                 int(env_offset), int(t), N.ptr(mask), N.ptr(out),
+                                                 N.current_stream_ptr(self.device)), "porl_qnet_act_rows_bcq")
+        return out
+
     def dist_learn_sampled(self, hp, states, actions, rewards, next_states, dones, n_rows, batch, seed, draw, head):
         """dist_learn on the rows engine.sample_indices(n_rows, batch, seed, draw) would give, drawn inside the gather
         launch (porl_qnet_dist_learn_sampled); the mean loss lands in stats[0]."""
@@ -1045,6 +1071,32 @@ def qnet_select(q, epsilon, seed, t, env_offset=0, out=None):
     out, q_rs = _select_args(q, out)
     N.check(N.lib().porl_qnet_select(N.ptr(q), q_rs, q.shape[1], q.shape[0], float(epsilon), int(seed) & (2 ** 64 - 1),
                                      int(env_offset), int(t), N.ptr(out), N.current_stream_ptr(q)), "porl_qnet_select")
+    return out
+
+
+def _bcq_select_args(q, logits, mask, out):
+    """_select_args for the value table, the same rules for the behaviour logits, and the optional dense (n, A) mask."""
+    out, q_rs = _select_args(q, out)
+    n, A = q.shape
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.device != q.device or logits.shape != (n, A) or \
+            (A > 1 and logits.stride(1) != 1):
+        raise RuntimeError(f"logits: need a ({n}, {A}) float32 table with unit column stride on {q.device}")
+    if mask is not None and (mask.dtype != torch.float32 or mask.device != q.device or mask.shape != (n, A) or
+                             not mask.is_contiguous()):
+        raise RuntimeError(f"mask: need a contiguous ({n}, {A}) float32 tensor on {q.device}")
+    return out, q_rs, (logits.stride(0) if n > 1 else max(logits.stride(0), A)), mask
+
+
+def bcq_select(q, logits, threshold, epsilon, seed, t, env_offset=0, mask=None, out=None):
+    """Epsilon-greedy actions (n,) int64 on the device under discrete BCQ's constraint (porl_bcq_select): from action values
+    `q` and behaviour logits `logits`, both (n, A <= 64) — the arg-max of q over the actions whose softmax probability
+    exceeds `threshold` (the learn step's expression q + (mask - 1) * 1e10), or with probability `epsilon` a uniform action
+    out of all A, drawn as qnet_select draws it.  `mask` (n, A) float32, optional, receives the 0 / 1 rows — the bits of
+    BehaviorPolicy.sample on the same logits.  Nothing is read back."""
+    out, q_rs, z_rs, mask = _bcq_select_args(q, logits, mask, out)
+    N.check(N.lib().porl_bcq_select(N.ptr(q), q_rs, N.ptr(logits), z_rs, q.shape[1], q.shape[0], float(threshold), float(epsilon),
+                                    int(seed) & (2 ** 64 - 1), int(env_offset), int(t), N.ptr(mask), N.ptr(out),
+                                    N.current_stream_ptr(q)), "porl_bcq_select")
     return out
 
 

@@ -83,6 +83,65 @@ def evaluate_policy_batched(act, sim, episodes, episode_step):
     return statistics.fmean(steps), statistics.fmean(scores), statistics.fmean(success)
 
 
+def evaluate_discrete(trainer, sim, episodes, episode_step=None, seed=0, constrained=True, poll_every=0):
+    """Score a trained agent of the discrete task (env/env.py) by its GREEDY policy: `episodes` episodes of at most
+    `episode_step` steps (default: the simulator's own limit) run in rounds of N = sim.n_envs, one episode per robot; the
+    last round counts the first robots only.  `sim`: a DiscreteLidarNavSim with auto_reset=False whose observation and
+    action count are the trainer's; `episode_step` may not exceed its step limit (ValueError).
+
+    Per round: sim.reset(), sim.tallies zeroed, then `episode_step` iterations of the act call the trainer's own vectorised
+    loop makes (train.vector_offline.batched_act) at epsilon 0, and sim.step.  For a BCQTrainer `constrained=True` scores the
+    policy its learn step's target assumes, False the plain arg-max the reference's trainer acts with.  `seed` keys the
+    fractions of an IQN agent (with sim.env_offset + i and the act-step, counted through the rounds).  A finished robot is
+    frozen by the step kernel, so when the round ends counters[:, 0] is every episode's length, the tallies hold return, goal
+    and hit of a finished episode and sim.returns the return of one still running: nothing is computed in torch inside the
+    loop, and one copy per round brings the results to the host.  `poll_every` = k > 0 adds one read-back of "every robot has
+    finished" after every k-th iteration and ends the round there; the results are the same.  The trainer's parameters,
+    epsilon, counters and replay are not touched.
+
+    Returns a dict: the means `steps` (episode length), `score` (summed reward), `success` (reached the goal), `hits`
+    (collided), `timeouts` (neither), and the per-episode numpy arrays `episode_steps`, `episode_scores`, `episode_goals`,
+    `episode_hits`."""
+    from .train.vector_offline import batched_act
+    if sim.auto_reset:
+        raise ValueError("evaluate_discrete needs a simulator with auto_reset=False")
+    if episode_step is None:
+        episode_step = int(sim.params["episode_step"])
+    if episodes < 1 or episode_step < 1 or poll_every < 0:
+        raise ValueError("episodes and episode_step must be positive, poll_every not negative")
+    _check_limit(episode_step, sim.params["episode_step"])
+    n, dev = sim.n_envs, sim.device
+    eng, A, act = batched_act(trainer, n, constrained=constrained)
+    if sim.obs_dim != eng.cfg.state_dim or sim.n_actions != A:
+        raise ValueError(f"the simulator observes {sim.obs_dim} floats and takes {sim.n_actions} actions; the trainer's network "
+                         f"maps {eng.cfg.state_dim} to {A}")
+    if sim.state.device != eng.device:
+        raise ValueError(f"simulator on {sim.state.device}, trainer on {eng.device}")
+    actions = torch.empty(n, dtype=torch.int64, device=dev)
+    rows, t0, left = [], 0, episodes
+    while left > 0:
+        take = min(n, left)
+        sim.reset()
+        sim.tallies.zero_()
+        for k in range(episode_step):
+            act(sim.obs, 0.0, seed, t0 + k, sim.env_offset, actions)
+            sim.step(actions)
+            if poll_every and (k + 1) % poll_every == 0 and bool(((sim.counters[:, 2] & 0xff) != 0).all()):
+                break
+        # a finished episode's return sits in its tallies row and its running return is 0; one still running the other way
+        host = torch.cat([sim.counters[:, :1].double(), sim.tallies[:, 1:2] + sim.returns[:, None], sim.tallies[:, 2:4]],
+                         dim=1)[:take].cpu().numpy()
+        rows.append(host)
+        left -= take
+        t0 += episode_step                                 # act-step numbers do not depend on where a poll ended a round
+    host = np.concatenate(rows, axis=0)
+    steps, scores, goals, hits = host[:, 0].astype(np.int64), host[:, 1].copy(), host[:, 2] != 0, host[:, 3] != 0
+    return dict(steps=statistics.fmean(steps.tolist()), score=statistics.fmean(scores.tolist()),
+                success=statistics.fmean(goals.tolist()), hits=statistics.fmean(hits.tolist()),
+                timeouts=statistics.fmean((~goals & ~hits).tolist()),
+                episode_steps=steps, episode_scores=scores, episode_goals=goals, episode_hits=hits)
+
+
 _command_consts: dict = {}
 
 

@@ -43,6 +43,22 @@ class BCQTrainer(DQNTrainer):
             return self.train_online(env, bcq_learn, num_episodes, max_steps)
         return self.train_offline(policy=policy, num_iterations=num_episodes)
 
+    def act_rows(self, states, epsilon, seed, t, env_offset=0, constrained=True, **scratch):
+        """Epsilon-greedy actions (n,) int64 on the device for n rows of states.  `constrained=True` (an extension over the
+        reference's trainer): the rule bcq_learn's target assumes — the best action among those the behaviour policy allows
+        at `self.threshold` (QnetEngine.act_rows_bcq; scratch q, logits, mask, out).  `constrained=False`: the plain arg-max
+        the reference's trainer acts with (QnetEngine.act_rows; scratch q, out).  Exploration is unconstrained either way."""
+        if not constrained:
+            return self._engine.act_rows(states, epsilon, seed, t, env_offset=env_offset, **scratch)
+        return self._engine.act_rows_bcq(self._behavior_engine, states, self.threshold, epsilon, seed, t, env_offset=env_offset,
+                                         **scratch)
+
+    def train_offline_device(self, replay, n_iters, **kw):
+        """Behaviour pre-training and `n_iters` BCQ steps on a DeviceReplay, nothing read back inside the loops
+        (train/vector_offline.py)."""
+        from .vector_offline import train_offline_device
+        return train_offline_device(self, replay, n_iters, **kw)
+
     def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):
         """dqn_trainer.py:119-180.  `policy=bcq_learn` (the function of porl_amd.policy.bcq): the loop with the BCQ rule
         bound to this trainer — greedy act and record on their one-launch forms, each learn step numpy's index draw into

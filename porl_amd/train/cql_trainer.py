@@ -306,6 +306,12 @@ class CQLTrainer:
         from .vector_online import train_vectorized
         return train_vectorized(self, sim, n_steps, **kw)
 
+    def train_offline_device(self, replay, n_iters, **kw):
+        """`n_iters` learn steps on a DeviceReplay with the minibatches drawn on the device and nothing read back inside the
+        loop (train/vector_offline.py).  PER trainers raise NotImplementedError."""
+        from .vector_offline import train_offline_device
+        return train_offline_device(self, replay, n_iters, **kw)
+
     # -- acting -----------------------------------------------------------------------------------
     def get_action(self, state: np.ndarray) -> int:
         x = torch.as_tensor(np.asarray(state), dtype=torch.float32, device=self.device).unsqueeze(0)

@@ -22,7 +22,7 @@ episode number does).
 Plain-Q trainers only: CQLTrainer, DQNTrainer, DDQNTrainer, DDDQNTrainer.  PERTrainer has the same loop around its own
 memory as `train_vectorized_per` (train/vector_per.py), C51Trainer and QRDQNTrainer around their own act and learn calls as
 `train_vectorized_dist` (train/vector_dist.py), IQNTrainer on its own engine as `train_vectorized_iqn`
-(train/vector_iqn.py); all three share `check_sim`, `check_starts` and `end_of_step` below.  BCQ is offline.
+(train/vector_iqn.py); all three share `check_sim`, `check_starts` and `end_of_step` below.  BCQ is offline: train/vector_offline.py.
 """
 from __future__ import annotations
 
