@@ -627,32 +627,87 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------
-// device sampler: `batch` DISTINCT row indices in [0, n) per call (uniform without replacement, like
-// np.random.choice(size, B, replace=False) in buffer/replay_buffer.py:64, but O(B) instead of O(N)):
-// index i is the image of i under a keyed pseudo-random permutation of [0, n) — a 4-round Feistel
-// network on 2*hb bits, cycle-walked into range.  Key = (seed, step).
+// device sampler: `batch` DISTINCT row indices in [0, n) per call, in the place of
+// np.random.choice(size, B, replace=False) in buffer/replay_buffer.py:64 but O(B) instead of O(N): index i is the
+// image of i under a keyed pseudo-random permutation of [0, n) — a Feistel network, cycle-walked into range.
+// Key = (seed, step).
+//
+// Guaranteed: for every key the map is a bijection of [0, n) (any `batch` positions give distinct rows, all n give
+// each row once), and positions first..first+count of one key are that slice of the whole permutation.
+// NOT guaranteed: that the n! permutations are equally likely — the keys are 32-bit hashes of (seed, step) and the
+// round function is a fixed hash, so this is a statistical stand-in for np.random.choice, not a cipher.  What is
+// tested (tests/test_sampler_host.py, on the integer mirror tests/helpers/sampler_cases.py that
+// tests/test_sampler_gpu.py holds every kernel here to, bit for bit): over 200 000 consecutive steps and stores of 2
+// to 4096 rows, and of 65 537 and 262 144 rows where the round count changes, chi-square statistics of the row at
+// position 0, of the rows of a batch of 8, of the pair at positions 0 and 1, of position 0 from one step to the next
+// and of the xor of two positions stay under the z = 5 quantile.
+//
+// Round count.  Four rounds leave the Luby-Rackoff structure: two positions that share a half collide in a round
+// function, and the xor of their images takes 2^hb single values twice as often as it should.  Over S batches that
+// adds S / 2^hb to a chi-square statistic of 4^hb cells, whose own deviation is sqrt(2) 2^hb: it shows once S
+// exceeds a few times n.  At S = 200 000 it is 250x the bound at small n, 1.5x at n = 4096, 2 sigma at hb = 8 and
+// half a sigma at hb = 9.  So:
+//   hb <= FEISTEL_SMALL_HB (n <= 65 536): FEISTEL_ROUNDS = 10 rounds.  The excess falls about 15x per two rounds —
+//     6 rounds still fail below 33 rows, 8 at 5 and 7 rows and are 2 sigma high at 17 to 32 — and with 10 nothing
+//     is left at this sample size.
+//   hb above that: 4 rounds, whose deviation a run shorter than a few n batches cannot show; these draws are bit for
+//     bit what they were before the small stores were fixed, and the entry chain of the one-launch step kernels
+//     (qnet_fused.hpp) pays nothing for the fix.
+// hb is a kernel argument, so the choice is uniform over a launch.
+//
+// Domain, ten-round form: hb low bits and `wa` high bits, wa = hb - 1 where hb >= 3 and 2^(2 hb - 1) >= n, else hb
+// (below 3 bits a narrower half mixes too slowly — 5 and 7 rows over 1 + 2 bits fail even with 12 rounds).  From 17
+// rows on the domain is < 2n, so a position leaves [0, n) with probability < 1/2 per walk step instead of < 3/4, which
+// is what decides how long the slowest lane of a wave walks.  Four-round form: 4^hb points, < 4n.
+//
+// Keys, ten-round form: round r of step s hashes the counter uint32(s) * 16 + r, so no two rounds of any 2^28
+// consecutive steps share a counter; the bits of s above 28 and the seed's two halves (by round parity) are hashed in
+// around it.  Four-round form: the counter uint32(s) * 4 + r, with the bits of s above 30 xored in between the two hashes.
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
   return x;
 }
 
+constexpr int FEISTEL_ROUNDS = 10;
+constexpr int FEISTEL_SMALL_HB = 8;
+static_assert(FEISTEL_ROUNDS % 2 == 0 && FEISTEL_ROUNDS <= 16, "even (the halves end where they began), and one counter in 16 each");
+
 __device__ __forceinline__ int64_t feistel_index(int64_t n, int64_t i, uint64_t seed, uint64_t step, int hb) {
-  const uint32_t mask = (1u << hb) - 1u;
-  uint32_t keys[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    keys[r] = mix32((uint32_t)(seed >> (r & 1 ? 32 : 0)) ^ mix32((uint32_t)step * 4u + r) ^ (uint32_t)(step >> 30));
-  // Cycle walking: apply the bijection of [0, 4^hb) until the image lands in [0, n).  The walk follows the cycle
-  // of i, which contains i < n itself, so it always ends (the domain is < 4n: fewer than 4 rounds on average) and
-  // the restriction to [0, n) is again a bijection — every position maps to a distinct row.
+  // Cycle walking (both forms): apply the bijection of the domain until the image lands in [0, n).  The walk follows
+  // the cycle of i, which contains i < n itself, so it always ends, and the restriction to [0, n) is again a
+  // bijection — every position maps to a distinct row.
   uint64_t x = (uint64_t)i;
-  do {
-    uint32_t L = (uint32_t)(x >> hb) & mask, R = (uint32_t)x & mask;
+  if (hb > FEISTEL_SMALL_HB) {
+    const uint32_t mask = (1u << hb) - 1u;
+    uint32_t keys[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const uint32_t f = mix32(R ^ keys[r]) & mask;
-      const uint32_t t = L ^ f;
+    for (int r = 0; r < 4; ++r)
+      keys[r] = mix32((uint32_t)(seed >> (r & 1 ? 32 : 0)) ^ mix32((uint32_t)step * 4u + r) ^ (uint32_t)(step >> 30));
+    do {
+      uint32_t L = (uint32_t)(x >> hb) & mask, R = (uint32_t)x & mask;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t f = mix32(R ^ keys[r]) & mask;
+        const uint32_t t = L ^ f;
+        L = R; R = t;
+      }
+      x = ((uint64_t)L << hb) | R;
+    } while ((int64_t)x >= n);
+    return (int64_t)x;
+  }
+  const int wa = hb >= 3 && ((int64_t)1 << (2 * hb - 1)) >= n ? hb - 1 : hb;
+  const uint32_t ma = (1u << wa) - 1u, mb = (1u << hb) - 1u;
+  const uint32_t top = mix32((uint32_t)(step >> 28)) ^ (uint32_t)(step >> 60);
+  uint32_t keys[FEISTEL_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < FEISTEL_ROUNDS; ++r)
+    keys[r] = mix32((uint32_t)(seed >> (r & 1 ? 32 : 0)) ^ mix32(((uint32_t)step * 16u + r) ^ top));
+  do {
+    uint32_t L = (uint32_t)(x >> hb), R = (uint32_t)x & mb;         // L: wa bits, R: hb bits; a round swaps the widths
+#pragma unroll
+    for (int r = 0; r < FEISTEL_ROUNDS; ++r) {
+      const uint32_t t = (L ^ mix32(R ^ keys[r])) & (r & 1 ? mb : ma);
       L = R; R = t;
     }
     x = ((uint64_t)L << hb) | R;

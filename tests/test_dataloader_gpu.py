@@ -87,9 +87,10 @@ def test_errors():
 
 @pytest.mark.parametrize("n", [2 ** 20 + 1, 2 ** 16 + 1, 4 ** 7, 1])
 def test_epoch_permutation_is_exact_just_above_a_power_of_four(n):
-    """The keyed permutation is a Feistel bijection on 4^hb >= n points, cycle-walked into [0, n): just above a power of
-    four the domain is almost 4x the range and many positions need several rounds (the round-1 version stopped after 64
-    rounds and fell back to the identity, which could duplicate a row — ADVICE r1).  Every position of an epoch must map
+    """The keyed permutation is a Feistel bijection on 2^(hb - 1 + hb) or 4^hb >= n points, cycle-walked into [0, n): just
+    above a power of four the half width grows, the domain is almost 4x the range (2x from 17 to 65 536 rows, where the
+    high half is a bit narrower) and many positions walk several times (the round-1 version stopped after 64 walk steps and fell back to the identity, which could
+    duplicate a row — ADVICE r1).  Every position of an epoch must map
     to a distinct row, for several keys."""
     import torch
     from porl_amd import engine as E
