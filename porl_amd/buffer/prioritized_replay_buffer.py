@@ -19,7 +19,7 @@ For the online loop (train/online.py) three one-launch forms sit beside them, bi
 without the gathers: data slots for the step kernel, weights, their mean, tree indices) and `update_priorities_device`
 (= `update_priorities` on a device fp32 tensor, e.g. the step kernel's |TD errors|).
 
-For a loop that writes N rows per launch (train/vector_per.py; csrc/per_vector.hpp) the buffer is also a WRITER in
+For a loop that writes N rows per launch (train/vector_online.py; csrc/per_vector.hpp) the buffer is also a WRITER in
 DeviceReplay's protocol — `states`, `next_states`, `state_dim`, `mirror()`, `position`, `advance(n)` — so
 `DiscreteLidarNavSim.step(actions, replay=memory)` writes the rows and `advance(n)` gives the n new leaves the priority
 `priority_for_new` by one launch (`fill_range`, porl_per_fill_range: bit-equal to `add(priority_for_new, ...)` n times and

@@ -150,6 +150,6 @@ class DistTrainerBase:
 
     def train_vectorized_dist(self, sim, n_steps, **kw):
         """act -> step -> learn with the N robots of a DiscreteLidarNavSim and no host synchronisation inside the loop:
-        train/vector_dist.py (`train_vectorized`, the plain-Q loop, keeps turning these trainers away)."""
-        from .vector_dist import train_vectorized_dist
+        train/vector_online.py (`train_vectorized`, the plain-Q loop, keeps turning these trainers away)."""
+        from .vector_online import train_vectorized_dist
         return train_vectorized_dist(self, sim, n_steps, **kw)

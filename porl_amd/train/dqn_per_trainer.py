@@ -55,8 +55,8 @@ class PERTrainer(CQLTrainer):
 
     def train_vectorized_per(self, sim, n_steps, **kw):
         """N robots of the discrete lidar task per step, this trainer's memory and learn step, no host synchronisation inside
-        the loop: train/vector_per.py.  (`train_vectorized`, the plain-Q loop, keeps turning this trainer away.)"""
-        from .vector_per import train_vectorized_per
+        the loop: train/vector_online.py.  (`train_vectorized`, the plain-Q loop, keeps turning this trainer away.)"""
+        from .vector_online import train_vectorized_per
         return train_vectorized_per(self, sim, n_steps, **kw)
 
     def train_online(self, env, policy=None, num_episodes: int = 1000, max_steps: int = 1000):

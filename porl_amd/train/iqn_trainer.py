@@ -23,7 +23,7 @@ parameters, gradients and Adam moments live in one flat buffer each (clip and Ad
 csrc/iqn_api.inc) on rows of the replay mirror: no autograd, no intermediate torch tensor, no host synchronisation inside
 the step.  The engine binds to the flat buffers above, so both paths share one state and may be interleaved.
 `train_online` runs on them (train/online.py:_FastIQN) when nothing the loop calls has been overridden;
-`train_vectorized_iqn` (train/vector_iqn.py) runs the same engine with N robots per step.
+`train_vectorized_iqn` (train/vector_online.py) runs the same engine with N robots per step.
 """
 from __future__ import annotations
 
@@ -292,6 +292,6 @@ class IQNTrainer:
 
     def train_vectorized_iqn(self, sim, n_steps, **kw):
         """act -> step -> learn with the N robots of a DiscreteLidarNavSim and no host synchronisation inside the loop:
-        train/vector_iqn.py (`train_vectorized`, the plain-Q loop, keeps turning this trainer away)."""
-        from .vector_iqn import train_vectorized_iqn
+        train/vector_online.py (`train_vectorized`, the plain-Q loop, keeps turning this trainer away)."""
+        from .vector_online import train_vectorized_iqn
         return train_vectorized_iqn(self, sim, n_steps, **kw)

@@ -25,42 +25,20 @@ import torch
 from .. import _native as N
 from .. import engine as E
 from ..buffer.device_replay import DeviceReplay
-from .vector_online import check_sim, learn_step
+from .vector_online import check_sim, draw_count, family_of, learn_step
 
 
 def batched_act(trainer, n_envs, constrained=True):
     """(engine, n_actions, act) for `trainer`: act(obs, epsilon, seed, t, env_offset, out) is the batched act call the
-    trainer's own vectorised loop makes for `n_envs` robots — QnetEngine.act_rows (plain Q and PER), act_rows_dist with
-    `_dist_head()` (C51, QR-DQN), IqnEngine.act_rows with num_quantiles_n_policy fractions per robot from the stream keyed by
-    the seed (IQN), BCQTrainer.act_rows(constrained=...) (BCQ).  The scratch tables are allocated once, here."""
-    from .bcq_trainer import BCQTrainer
-    from .cql_trainer import CQLTrainer
-    from .dist_trainer import DistTrainerBase
-    from .iqn_trainer import IQNTrainer
-    A = trainer.action_size
-    if isinstance(trainer, IQNTrainer):
-        from .vector_iqn import MAX_CHUNK
-        eng = trainer._native_engine(batch=max(trainer.batch_size, min(n_envs, MAX_CHUNK)))
-    elif isinstance(trainer, (CQLTrainer, DistTrainerBase)):
-        eng = trainer._engine
-        eng._ensure_bound()
-    else:
+    trainer's family makes in the vectorised loop for `n_envs` robots (the family table of train/vector_online.py), with its
+    scratch tables allocated once, here.  `constrained` is BCQTrainer.act_rows's."""
+    fam = family_of(type(trainer))
+    if fam is None:
         raise NotImplementedError(f"{type(trainer).__name__} has no batched act call in the discrete task")
-    q = torch.empty(n_envs, A, dtype=torch.float32, device=eng.device)
-    if isinstance(trainer, BCQTrainer):
-        scratch = dict(q=q, logits=torch.empty_like(q)) if constrained else dict(q=q)
-        act = lambda obs, epsilon, seed, t, env_offset, out: trainer.act_rows(
-            obs, epsilon, seed, t, env_offset=env_offset, constrained=constrained, out=out, **scratch)
-    elif isinstance(trainer, IQNTrainer):
-        K = trainer.num_quantiles_n_policy
-        act = lambda obs, epsilon, seed, t, env_offset, out: eng.act_rows(obs, K, epsilon, seed, t, env_offset=env_offset, q=q, out=out)
-    elif isinstance(trainer, DistTrainerBase):
-        head = trainer._dist_head()
-        act = lambda obs, epsilon, seed, t, env_offset, out: eng.act_rows_dist(obs, head, epsilon, seed, t, env_offset=env_offset,
-                                                                               q=q, out=out)
-    else:
-        act = lambda obs, epsilon, seed, t, env_offset, out: eng.act_rows(obs, epsilon, seed, t, env_offset=env_offset, q=q, out=out)
-    return eng, A, act
+    eng = fam.engine(trainer, n_envs)
+    if hasattr(eng, "_ensure_bound"):
+        eng._ensure_bound()
+    return eng, trainer.action_size, fam.act(trainer, eng, n_envs, constrained)
 
 
 def collect_discrete(sim, replay, n_steps, trainer=None, epsilon=1.0, seed=0, t0=0):
@@ -113,9 +91,9 @@ def _refuse(trainer):
 
 
 def _next_draw(trainer):
-    trainer._draws = getattr(trainer, "_draws", 0)
-    trainer._draws += 1
-    return trainer._draws - 1
+    draw = draw_count(trainer)
+    trainer._draws = draw + 1
+    return draw
 
 
 def train_offline_device(trainer, replay, n_iters, seed=0, pretrain=None):

@@ -321,7 +321,7 @@ def test_refusals(tmp_path):
     from porl_amd.train.c51_trainer import C51Trainer
     from porl_amd.train.dqn_trainer import DQNTrainer
     from porl_amd.train.qr_dqn_trainer import QRDQNTrainer
-    from porl_amd.train.vector_dist import train_vectorized_dist
+    from porl_amd.train.vector_online import train_vectorized_dist
     sim = make_sim()
     dqn = DQNTrainer(S, A, 0.99, device=DEV, batch_size=B, log_dir=str(tmp_path))
     with pytest.raises(NotImplementedError, match="C51Trainer and QRDQNTrainer"):

@@ -93,7 +93,7 @@ def test_python_surface_refuses_without_a_device(tmp_path):
     from porl_amd.train.c51_trainer import C51Trainer
     from porl_amd.train.dist_trainer import DistTrainerBase
     from porl_amd.train.dqn_trainer import DQNTrainer
-    from porl_amd.train.vector_dist import train_vectorized_dist
+    from porl_amd.train.vector_online import train_vectorized_dist
     assert callable(E.dist_select) and callable(E.QnetEngine.act_rows_dist) and callable(E.QnetEngine.dist_learn_sampled)
     assert callable(DistTrainerBase.train_vectorized_dist) and C51Trainer.train_vectorized_dist is DistTrainerBase.train_vectorized_dist
     with pytest.raises(RuntimeError, match="HIP device"):

@@ -373,7 +373,7 @@ def test_refusals(tmp_path):
     from porl_amd.buffer.device_replay import DeviceReplay
     from porl_amd.train.dqn_trainer import DQNTrainer
     from porl_amd.train.iqn_trainer import IQNTrainer
-    from porl_amd.train.vector_iqn import train_vectorized_iqn
+    from porl_amd.train.vector_online import train_vectorized_iqn
     sim = make_sim()
     sim_before = [x.clone() for x in (sim.state, sim.counters, sim.obs, sim.tallies)]
     dqn = DQNTrainer(S, A, 0.99, device=DEV, batch_size=B, log_dir=str(tmp_path))

@@ -225,7 +225,7 @@ def test_python_surface_refuses_without_a_device(tmp_path):
     from porl_amd import engine as E
     from porl_amd.train.dqn_trainer import DQNTrainer
     from porl_amd.train.iqn_trainer import IQNTrainer
-    from porl_amd.train.vector_iqn import train_vectorized_iqn
+    from porl_amd.train.vector_online import train_vectorized_iqn
     assert callable(E.iqn_draw_taus) and callable(E.iqn_select_rows) and callable(E.IqnEngine.act_rows)
     assert callable(E.IqnEngine.learn_sampled) and callable(IQNTrainer.train_vectorized_iqn)
     with pytest.raises(RuntimeError, match="HIP device"):

@@ -240,3 +240,35 @@ def test_python_surface_has_no_cpu_path():
     import sys
     assert "gymnasium" not in sys.modules and "rospy" not in sys.modules
     assert torch is not None
+
+
+def test_family_table_takes_each_trainer_class_once():
+    """train/vector_online.py's table on the classes alone (PER and IQN trainers need a device to exist): PER and BCQ
+    subclass CQLTrainer and must be found before plain Q; a subclass stays in its base's family."""
+    from porl_amd.train import vector_online as VO
+    from porl_amd.train.bcq_trainer import BCQTrainer
+    from porl_amd.train.c51_trainer import C51Trainer
+    from porl_amd.train.cql_trainer import CQLTrainer
+    from porl_amd.train.dddqn_trainer import DDDQNTrainer
+    from porl_amd.train.dist_trainer import DistTrainerBase
+    from porl_amd.train.dqn_per_trainer import PERTrainer
+    from porl_amd.train.dqn_trainer import DDQNTrainer, DQNTrainer
+    from porl_amd.train.iqn_trainer import IQNTrainer
+    from porl_amd.train.qr_dqn_trainer import QRDQNTrainer
+    from porl_amd.train.vector_offline import batched_act
+    assert issubclass(PERTrainer, CQLTrainer) and issubclass(BCQTrainer, CQLTrainer)
+    want = {VO.PLAIN: (CQLTrainer, DQNTrainer, DDQNTrainer, DDDQNTrainer), VO.PER: (PERTrainer,), VO.BCQ: (BCQTrainer,),
+            VO.DIST: (DistTrainerBase, C51Trainer, QRDQNTrainer), VO.IQN: (IQNTrainer,)}
+    assert set(want) == set(VO.FAMILIES) and len(VO.FAMILIES) == 5
+    for fam, classes in want.items():
+        for cls in classes:
+            assert VO.family_of(cls) is fam, cls.__name__
+            assert VO.family_of(type("Sub", (cls,), {})) is fam, cls.__name__
+    assert VO.family_of(object) is None and VO.family_of(type(None)) is None
+    # every family with a loop names it and has a learn step; BCQ has an act call only
+    loops = {fam.loop: fam for fam in VO.FAMILIES if fam.loop}
+    assert sorted(loops) == ["train_vectorized", "train_vectorized_dist", "train_vectorized_iqn", "train_vectorized_per"]
+    assert all(callable(fam.learn) and callable(getattr(VO, name)) for name, fam in loops.items())
+    assert VO.BCQ.loop is None and VO.BCQ.learn is None and all(callable(fam.act) for fam in VO.FAMILIES)
+    with pytest.raises(NotImplementedError, match="object has no batched act call in the discrete task"):
+        batched_act(object(), 8)

@@ -322,7 +322,7 @@ def test_refusals_advance_nothing(tmp_path):
     from porl_amd.env import DiscreteLidarNavSim, NavWorld
     from porl_amd.train.dqn_trainer import DQNTrainer
     from porl_amd.train.dqn_per_trainer import PERTrainer
-    from porl_amd.train.vector_per import train_vectorized_per
+    from porl_amd.train.vector_online import train_vectorized_per
     t, sim = make_trainer("mean_weight", tmp_path), make_sim()
     with pytest.raises(ValueError, match="auto_reset"):
         t.train_vectorized_per(DiscreteLidarNavSim(NavWorld.lattice(), 8, n_beams=N_BEAMS), 4)

@@ -188,3 +188,71 @@ def test_refusals(tmp_path):
     with pytest.raises(ValueError, match="learning_starts"):
         t.train_vectorized(sim, 4, replay=DeviceReplay(100, S, DEV), learning_starts=101)
     assert t.optimizer.step_count == 0 and not hasattr(t, "_vec_steps")     # a refused call advanced nothing
+
+
+# ---- every entry point against every trainer family: the one that matches runs, the others are refused untouched ------------
+ENTRY_OF = {"dqn": "train_vectorized", "per": "train_vectorized_per", "c51": "train_vectorized_dist", "qr": "train_vectorized_dist",
+            "iqn": "train_vectorized_iqn", "bcq": None}
+MATRIX_ENVS, MATRIX_B, MATRIX_STEPS, MATRIX_STARTS = 8, 8, 4, 16
+
+
+def make_any_trainer(kind, tmp_path):
+    from porl_amd.net.q_network import QNetwork
+    torch.manual_seed(0)
+    kw = dict(device=DEV, batch_size=MATRIX_B, log_dir=str(tmp_path))
+    net = lambda s, a: QNetwork(s, a, [64, 64])
+    if kind == "dqn":
+        from porl_amd.train.dqn_trainer import DQNTrainer
+        return DQNTrainer(S, A, 0.99, network=net, **kw)
+    if kind == "per":
+        from porl_amd.train.dqn_per_trainer import PERTrainer
+        return PERTrainer(S, A, 0.99, network=net, capacity=200, **kw)
+    if kind == "bcq":
+        from porl_amd.train.bcq_trainer import BCQTrainer
+        return BCQTrainer(S, A, 0.99, network=net, **kw)
+    if kind == "c51":
+        from porl_amd.train.c51_trainer import C51Trainer
+        return C51Trainer(S, A, 0.99, atom_size=11, network_hidden_sizes=[64, 64], **kw)
+    if kind == "qr":
+        from porl_amd.train.qr_dqn_trainer import QRDQNTrainer
+        return QRDQNTrainer(S, A, 0.99, num_quantiles=12, network_hidden_sizes=[64, 64], **kw)
+    from porl_amd.train.iqn_trainer import IQNTrainer
+    return IQNTrainer(S, A, 0.99, embedding_dim=10, hidden_size=64, num_quantiles_n_policy=6, num_quantiles_n_prime_loss=3,
+                      num_quantiles_n_double_prime_loss=5, **kw)
+
+
+@pytest.mark.parametrize("kind", list(ENTRY_OF))
+@pytest.mark.parametrize("entry", ["train_vectorized", "train_vectorized_per", "train_vectorized_dist", "train_vectorized_iqn"])
+def test_refusal_matrix(entry, kind, tmp_path):
+    """8 robots, hidden [64, 64], 4 steps, on a simulator and a replay that two random steps have already moved.  The entry
+    point of the trainer's family runs, learning from 16 rows on; every other pair raises NotImplementedError and leaves the
+    trainer's counters, the optimizer, the simulator and the replay as they were.  BCQ has no online entry point."""
+    from porl_amd.buffer.device_replay import DeviceReplay
+    from porl_amd.env import DiscreteLidarNavSim, NavWorld
+    from porl_amd.train import vector_online as VO
+    from porl_amd.train.vector_offline import collect_discrete
+    t = make_any_trainer(kind, tmp_path)
+    sim = DiscreteLidarNavSim(NavWorld.lattice(), MATRIX_ENVS, n_actions=A, seed=3, auto_reset=True, n_beams=N_BEAMS, episode_step=20)
+    replay = DeviceReplay(200, S, DEV)
+    collect_discrete(sim, replay, 2, seed=SEED)
+    assert len(replay) == 2 * MATRIX_ENVS and bool(replay.states[:len(replay)].any())
+    kw = dict(learning_starts=MATRIX_STARTS, block=2, seed=SEED)
+    if entry != "train_vectorized_per":
+        kw["replay"] = replay
+    if entry == ENTRY_OF[kind]:
+        out = getattr(VO, entry)(t, sim, MATRIX_STEPS, **kw)
+        assert {"learn_steps", "transitions", "losses", "tallies"} <= set(out)
+        assert out["transitions"] == MATRIX_ENVS * MATRIX_STEPS and out["tallies"].shape == (4,)
+        # PER fills its own empty memory, 16 rows after the second step: 3 learn steps; the others find 16 rows waiting: 4
+        assert out["learn_steps"] == len(out["losses"]) == t.optimizer.step_count == t._draws == (3 if kind == "per" else 4)
+        assert bool(torch.isfinite(torch.from_numpy(out["losses"])).all()) and t._vec_steps == MATRIX_STEPS
+        return
+    held = [sim.counters, sim.state, *replay.arrays()]
+    if kind == "per":
+        held += [t.memory.tree, *t.memory.arrays()]
+    before = [x.clone() for x in held]
+    with pytest.raises(NotImplementedError):
+        getattr(VO, entry)(t, sim, MATRIX_STEPS, **kw)
+    assert not hasattr(t, "_vec_steps") and not hasattr(t, "_draws") and not hasattr(t, "device_replay")
+    assert t.optimizer.step_count == 0 and len(replay) == 2 * MATRIX_ENVS
+    assert all(torch.equal(x, y) for x, y in zip(before, held))
