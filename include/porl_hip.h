@@ -1174,6 +1174,60 @@ int porl_qnet_act_rows_bcq(porl_qnet* h, porl_qnet* beh, int which, const float*
                            int64_t q_rs, float* logits, int64_t z_rs, float threshold, double epsilon, uint64_t seed,
                            int64_t env_offset, uint64_t t, float* mask, int64_t* out, void* stream);
 
+/* ---- An A* expert for the navigation task, planned on the device (csrc/expert.hpp) ------------------------------------
+ * The device form of the reference's dataloader/a_star.py AStarPlanner.planning for n robots per call, with no read-back.
+ * Grid: w x h cells, the centre of cell (ix, iy) at ix * resolution + min_x, iy * resolution + min_y (a product, then a
+ * sum); the cell of a position is rint((x - min_x) / resolution), half to even.  A cell is blocked iff its centre lies
+ * within `inflate` of a primitive of the world (segments (M, 4), circles (C, 3) fp32 as porl_nav_scan reads them, widened
+ * to fp64; a segment of length 0 is a point).  Limits: (w + 2)(h + 2) <= 65536 padded cells, the padded field and the
+ * bitmap within one workgroup's LDS (porl_astar_label's limit), w + h <= 65534. */
+typedef struct porl_nav_grid {
+  double resolution;    /* > 0 */
+  double inflate;       /* >= 0: the clearance kept from every primitive */
+  double min_x, min_y;  /* centre of cell (0, 0) */
+  int32_t w, h;
+} porl_nav_grid;
+#define PORL_EXPERT_OK 0             /* a waypoint was found */
+#define PORL_EXPERT_NO_FIELD 1       /* the robot's cell is off the grid, or it and its eight neighbours are unreached */
+#define PORL_EXPERT_GOAL_OFF_GRID 2
+#define PORL_EXPERT_GOAL_BLOCKED 3
+#define PORL_EXPERT_NON_FINITE 4     /* pose or goal */
+#define PORL_EXPERT_NOT_CONVERGED 5  /* the field kernel reached its sweep bound of w * h */
+typedef struct porl_nav_expert_params {
+  double dt;            /* porl_nav_params.dt */
+  double max_lin_vel;   /* porl_nav_params.max_lin_vel: v = max_lin_vel * max(0, cos e) */
+  double max_ang_vel;   /* porl_nav_params.max_ang_vel: w = clip(e / dt, +-max_ang_vel) */
+  double ang_step;      /* porl_nav_discrete.ang_step (scores only) */
+  int32_t n_actions;    /* porl_nav_discrete.n_actions, 1 .. 64 (scores only) */
+  int32_t lookahead;    /* >= 1: the waypoint is the centre of the cell this many steps down the path */
+  int32_t max_path;     /* >= 0: cells written per robot when path is given */
+  int32_t reserved;     /* 0 */
+} porl_nav_expert_params;
+/* The occupancy bitmap of a world: bit (iy + 1) * (w + 2) + ix + 1 of n_words >= ceil((w + 2)(h + 2) / 32) uint32 words on
+ * the device (porl_astar_label's padded layout; halo bits read 0).  One launch. */
+int porl_nav_rasterize(const float* segments, int32_t M, const float* circles, int32_t C, const porl_nav_grid* grid,
+                       uint32_t* bitmap, int64_t n_words, void* stream);
+/* Plan and steer n robots from state (n, 8) fp64 `x y yaw goal_x goal_y ...` (porl_nav_step's), two launches on `stream`.
+ * (1) Robot i whose goal cell is on the grid and free and differs from the one tag[i] names gets its exact 8-connected
+ * distance field from the goal cell — pairs a << 16 | b, 0xFFFFFFFF unreached, (w + 2)(h + 2) uint32 in row i of `field` —
+ * and tag[i] = iy * w + ix + 1 of the goal cell (tag (n) int64, 0 = no field; start from zeros); every other robot's row
+ * and tag stay as they are.  (2) Every robot: status (above); for PORL_EXPERT_OK the path is the descent of the field
+ * from the robot's cell in the reference's motion order — the first neighbour n with field[n] + move == field[c] as
+ * integers; from an unreached cell the first step goes to its reached neighbour of least cost — path_len the node count
+ * from the robot's cell to the goal's, both included, and the waypoint the centre of the cell `lookahead` steps down, or
+ * the goal position itself once the descent reaches the goal cell.  For every other status the waypoint is the goal
+ * position and path_len 0.  With e the heading error to the waypoint wrapped into [-pi, pi]: commands (n, 2) fp32 with row
+ * stride cmd_stride `v = max_lin_vel * max(0, cos e), w = clip(e / dt, +-max_ang_vel)`; scores (n, n_actions) fp32 with row
+ * stride score_stride `-|e - w_a dt|`, w_a = ((n_actions - 1) / 2 - a) * ang_step, porl_nav_dstep's command table, so
+ * porl_qnet_select on them picks the nearest turn.  PORL_EXPERT_NON_FINITE: zero command, zero scores.  path (n, max_path,
+ * 2) int32 receives the cells (ix, iy) from the robot's to the goal's, truncated at max_path, the rest -1.  commands,
+ * scores, waypoint (n, 2) fp64, path_len (n), status (n) and path are each optional (NULL).  Robots that are not running
+ * are planned from the state they hold.  Nothing is read back; every argument is checked before the first launch. */
+int porl_nav_expert(const porl_nav_grid* grid, const uint32_t* bitmap, const porl_nav_expert_params* params,
+                    const double* state, uint32_t* field, int64_t* tag, float* commands, int64_t cmd_stride, float* scores,
+                    int64_t score_stride, double* waypoint, int32_t* path_len, int32_t* status, int32_t* path, int64_t n,
+                    void* stream);
+
 /* Experiment knobs (scheduling only, never the mathematics).  "gemm_lds_pad": extra dynamic LDS bytes per GEMM block,
  * limiting how many blocks share a CU.  "qnet_fused": 0 forces the multi-launch CQL path.  porl_tune_set sets the process
  * defaults, copied by porl_iql / qnet / enc handles when created; porl_iql_tune_set sets one live IQL engine's copy. */

@@ -48,6 +48,7 @@ SYMBOLS = [
     "porl_dist_select", "porl_qnet_act_rows_dist", "porl_qnet_dist_learn_sampled",
     "porl_iqn_draw_taus", "porl_iqn_select_rows", "porl_iqn_act_rows", "porl_iqn_learn_sampled",
     "porl_bcq_select", "porl_qnet_act_rows_bcq",
+    "porl_nav_rasterize", "porl_nav_expert",
 ]
 
 
@@ -162,6 +163,15 @@ class NavParams(C.Structure):
 class NavDiscrete(C.Structure):
     _fields_ = [("n_actions", C.c_int32), ("lin_vel", C.c_double), ("ang_step", C.c_double), ("goal_reward", C.c_double),
                 ("hit_reward", C.c_double)]
+
+
+class NavGrid(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("resolution", "inflate", "min_x", "min_y")] + [("w", C.c_int32), ("h", C.c_int32)]
+
+
+class NavExpertParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("dt", "max_lin_vel", "max_ang_vel", "ang_step")] + \
+               [(n, C.c_int32) for n in ("n_actions", "lookahead", "max_path", "reserved")]
 
 
 class ProfEntry(C.Structure):
@@ -349,6 +359,9 @@ def _declare(lib):
     lib.porl_bcq_select.argtypes = [vp, i64, vp, i64, i32, i64, f32, f64, C.c_uint64, i64, C.c_uint64, vp, vp, vp]
     lib.porl_qnet_act_rows_bcq.argtypes = [vp, vp, C.c_int, vp, i64, i64, vp, i64, vp, i64, f32, f64, C.c_uint64, i64,
                                            C.c_uint64, vp, vp, vp]
+    lib.porl_nav_rasterize.argtypes = [vp, i32, vp, i32, C.POINTER(NavGrid), vp, i64, vp]
+    lib.porl_nav_expert.argtypes = [C.POINTER(NavGrid), vp, C.POINTER(NavExpertParams), vp, vp, vp, vp, i64, vp, i64, vp, vp, vp,
+                                    vp, i64, vp]
     lib.porl_prof_enable.argtypes = [C.c_int]
     lib.porl_prof_read.argtypes = [C.POINTER(ProfEntry), C.c_int]
     for name in SYMBOLS:

@@ -251,6 +251,35 @@ def build_sanitized_per_vector(force=False, verbose=True):
     return SAN_PER_VECTOR_DRIVER
 
 
+# ninth driver, built the same way: the A* expert's entry points (tests/test_expert_host.py)
+SAN_EXPERT_DRIVER_SRC = os.path.join(os.path.dirname(HERE), "tests", "helpers", "abi_reject_expert.cpp")
+SAN_EXPERT_DRIVER = os.path.join(HERE, "lib", "abi_reject_expert_san")
+
+
+def build_sanitized_expert(force=False, verbose=True):
+    """tests/helpers/abi_reject_expert.cpp -> SAN_EXPERT_DRIVER, a stand-alone program linked against the host-only
+    sanitized library of `build_sanitized` (built first when it is not current).  Cached by the hash of the library's
+    sources and the driver's.  Returns SAN_EXPERT_DRIVER."""
+    import hashlib
+    build_sanitized(force=force, verbose=verbose)
+    h = hashlib.sha256((source_hash() + open(SAN_EXPERT_DRIVER_SRC).read()).encode()).hexdigest()
+    tag = SAN_EXPERT_DRIVER + ".srchash"
+    try:
+        if not force and os.path.exists(SAN_EXPERT_DRIVER) and open(tag).read().strip() == h:
+            return SAN_EXPERT_DRIVER
+    except OSError:
+        pass
+    clangxx = os.path.join(os.path.dirname(os.path.dirname(hipcc())), "lib", "llvm", "bin", "clang++")
+    cmd = [clangxx if os.path.exists(clangxx) else "clang++", "-std=c++17", "-O1", "-g", *SAN_FLAGS, "-o", SAN_EXPERT_DRIVER,
+           SAN_EXPERT_DRIVER_SRC, SAN_OUT, "-Wl,-rpath," + os.path.dirname(SAN_OUT)]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL if not verbose else None)
+    with open(tag, "w") as f:
+        f.write(h + "\n")
+    return SAN_EXPERT_DRIVER
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     print(OUT)
@@ -263,3 +292,4 @@ if __name__ == "__main__":
         print(build_sanitized_goal_bc(force="--force" in sys.argv))
         print(build_sanitized_navsim(force="--force" in sys.argv))
         print(build_sanitized_per_vector(force="--force" in sys.argv))
+        print(build_sanitized_expert(force="--force" in sys.argv))

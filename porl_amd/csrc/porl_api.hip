@@ -34,6 +34,7 @@
 #include "dist_act.hpp"
 #include "iqn_vector.hpp"
 #include "bcq_act.hpp"
+#include "expert.hpp"
 
 using namespace porl;
 
@@ -878,4 +879,5 @@ int porl_prof_read(porl_prof_entry* out, int max_entries) {
 #include "colstats_api.inc"
 #include "navsim_api.inc"
 #include "navsim_discrete_api.inc"
+#include "expert_api.inc"
 #include "per_vector_api.inc"

@@ -5,7 +5,8 @@ without stepping, and hand every trainer family one batched act call (evaluate.e
                         straight into a DeviceReplay.  Without a trainer every action is the exploration draw of
                         porl_qnet_select — the device form of collect_dataset's random policy (reference policy/bcq.py:8-20);
                         with a trainer of any family that family's batched act call at `epsilon`, which is how a behaviour
-                        data set of mixed quality is made.
+                        data set of mixed quality is made; with `expert`, an env.expert.AStarExpert of the simulator, the
+                        expert's score table under the same epsilon-greedy rule: goal-reaching data without a trained agent.
   train_offline_device  the reference's offline pipeline after the collection (scripts/train_bcq.py: bcq_behavior_pretrain,
                         then bcq_learn in DQNTrainer.train_offline's loop) on a DeviceReplay: the choices of
                         bcq_pretrain_device_sampled and bcq_learn_device_sampled (policy/bcq.py) with the replay arrays in place
@@ -41,19 +42,32 @@ def batched_act(trainer, n_envs, constrained=True):
     return eng, trainer.action_size, fam.act(trainer, eng, n_envs, constrained)
 
 
-def collect_discrete(sim, replay, n_steps, trainer=None, epsilon=1.0, seed=0, t0=0):
+def collect_discrete(sim, replay, n_steps, trainer=None, epsilon=1.0, seed=0, t0=0, expert=None):
     """Run `n_steps` iterations of act -> sim.step(actions, replay=replay) with `sim`, a DiscreteLidarNavSim with
     auto_reset=True, and `replay`, a DeviceReplay of its observation width and at least its robot count.  `trainer=None`:
     uniform random actions (engine.qnet_select with epsilon 1 on a dummy value table, no forward); else the trainer's batched
-    act call (`batched_act`) at `epsilon` — the trainer is read, never modified.  Act-step k of this call is `t0 + k`: with
+    act call (`batched_act`) at `epsilon` — the trainer is read, never modified.  `expert` (without a trainer; both: ValueError):
+    an AStarExpert of `sim`; the act is `expert()` into a scratch table, then engine.qnet_select on it at `epsilon` — the nearest
+    turn to the planned waypoint, or with probability epsilon the same uniform draw (epsilon 1: the random policy, action for
+    action).  Act-step k of this call is `t0 + k`: with
     `seed` and sim.env_offset + i it keys robot i's exploration draws, so a later call continues with t0 advanced by n_steps.
     Returns, after the one read-back, dict(transitions, tallies) — tallies (numpy (4,)): sim.tallies summed over robots."""
     if n_steps < 1 or t0 < 0:
         raise ValueError("n_steps must be positive, t0 not negative")
     if not 0.0 <= epsilon <= 1.0:
         raise ValueError("epsilon must lie in [0, 1]")
+    if expert is not None and trainer is not None:
+        raise ValueError("collect_discrete: pass a trainer or an expert, not both")
     N_, dev = sim.n_envs, sim.device
-    if trainer is None:
+    if expert is not None:
+        if not sim.auto_reset:
+            raise ValueError("collect_discrete needs a simulator with auto_reset=True")
+        if expert.sim is not sim or not expert.discrete:
+            raise ValueError("collect_discrete: the expert must have been made for this DiscreteLidarNavSim")
+        table = torch.empty(N_, sim.n_actions, dtype=torch.float32, device=dev)
+        act = lambda obs, eps, seed_, t, env_offset, out: E.qnet_select(expert(out=table), eps, seed_, t, env_offset=env_offset,
+                                                                         out=out)
+    elif trainer is None:
         if not sim.auto_reset:
             raise ValueError("collect_discrete needs a simulator with auto_reset=True")
         dummy = torch.zeros(N_, sim.n_actions, dtype=torch.float32, device=dev)
