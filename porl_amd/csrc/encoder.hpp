@@ -72,10 +72,8 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restric
 // Pixel semantics are costmap_kernel's (kernels.hpp): values > 8 read as 0, beams rolled by n_ang/2, distance bin
 // 0 cleared, python-style wrap of the cross at bin -1.
 // Both kernels only READ the state, through a RowSrc (kernels.hpp): a dense (batch, n_ang + 2) tensor, or rows of a
-// packed replay store picked by an index array and a column offset.
+// packed replay store picked by an index array and a column offset.  The geometry is costmap_geom's (kernels.hpp).
 // ---------------------------------------------------------------------------------------------------
-struct CostmapGeom { int n_ang, n_dist; float dist_inc, ang_inc, deg_min, deg_max, dist_max; };
-
 // marks the set pixels of patch row py of sample `st` in mask[Wp] (LDS, zeroed by the caller); threads 0..3 take
 // the four beams of the strip, thread 4 the goal cross
 __device__ __forceinline__ void patch_row_masks(const float* __restrict__ st, const CostmapGeom& g, int py,
@@ -470,6 +468,10 @@ struct PconvMfmaArgs {
   int C, Hh, Ww, tiles_per_sample, tiles_total, tiles_per_block;
 };
 
+// floats of one 32-channel pass of that image, [tap][32][CP + 4] (what the kernel parks in LDS), and of all its passes
+constexpr int pconv_mfma_pass_floats(int cp) { return 9 * 32 * (cp + 4); }
+constexpr int pconv_mfma_passes(int cp) { return (cp + 31) / 32; }
+constexpr int pconv_mfma_image_floats(int cp) { return pconv_mfma_passes(cp) * pconv_mfma_pass_floats(cp); }
 __global__ void pack_pconv_mfma_kernel(const float* __restrict__ src, float* __restrict__ dst, int CP, int npass) {
   const int XS = CP + 4, n = npass * 9 * 32 * XS;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {

@@ -6,11 +6,18 @@
 //   -> MLPBlock(2E) x depth1 -> global average pool -> 1x1 (2E -> feature_dim) + ReLU -> Linear(+bias)
 // MLPBlock: y = [PConv3x3(x[:, :C/n_div]) | x[:, C/n_div:]];  x += drop_scale * W2 relu(BN(W1 y))
 // Every convolution except the 4x4 patch embedding is a grouped fp32-MFMA GEMM over position rows.
+//
+// enc_forward_src is that sequence, one host function per step; fp32 or bf16 activations (`fused16`) is an `if` inside a step:
+//   enc_pack_weights (if stale) -> enc_patch_embed (sparse | dense) -> enc_stage (enc_block | enc_block_bf16) -> enc_merge
+//   (enc_merge_bf16 | enc_merge_gather | enc_merge_s2d, + BatchNorm) -> enc_stage -> enc_pool -> enc_head
+// Packed weight images are sized by the functions beside their pack kernels; LDS limits are raised by dyn_lds_once alone.
 
 #include "encoder.hpp"
 #include "encoder_bf16.hpp"
 
 namespace {
+
+constexpr int ENC_LDS_LIMIT = 150 * 1024;   // the most dynamic LDS an encoder kernel is launched with (160 KiB per CU)
 
 struct EncBn {
   int C = 0;
@@ -81,7 +88,7 @@ int64_t enc_ws(porl_enc* h, int64_t n) {
 // The forward's two branch predicates, shared with porl_enc_tap_info so the query cannot drift from what ran.
 // sparse patch embedding: straight from the lidar state (weight + one patch row of masks fit in LDS)
 bool enc_sparse_patch(const porl_enc* h) {
-  return h->E <= PE_MAX_E && !h->tune.enc_dense_patch && (size_t)PE_K * h->E * sizeof(float) + (size_t)h->P1 * 12 <= 150 * 1024;
+  return h->E <= PE_MAX_E && !h->tune.enc_dense_patch && (size_t)PE_K * h->E * sizeof(float) + (size_t)h->P1 * 12 <= ENC_LDS_LIMIT;
 }
 // bf16-activation mode: needs the sparse patch embedding (it writes bf16 directly); otherwise the bf16-operand mode
 bool enc_fused16(const porl_enc* h) { return h->bf16_fused && enc_sparse_patch(h) && !h->tune.enc_bf16_operands_only; }
@@ -142,6 +149,15 @@ int enc_gemm_rows(const porl_enc* h, hipStream_t s, const float* A, int lda, lon
   return 0;
 }
 
+// `nblocks` partial sums (eval: none, the running statistics) -> bn's folded scale / shift.  The caller owns the ProfScope.
+int enc_bn_finish(porl_enc* h, const EncBn& bn, const double* partial, int nblocks, long rows, int training, hipStream_t s) {
+  hipLaunchKernelGGL(bn_finish_kernel, dim3(bn.C), dim3(64), 0, s, partial, nblocks, bn.C, rows, h->params + bn.gamma,
+                     h->params + bn.bias, h->stats + bn.mean, h->stats + bn.var, training, (double)h->cfg.bn_eps,
+                     (double)h->cfg.bn_momentum, h->W + bn.alpha, h->W + bn.beta);
+  PORL_HIP(hipGetLastError());
+  return 0;
+}
+
 // apply = false: only the statistics and the folded scale / shift (W + bn.alpha, W + bn.beta) are produced; the
 // consumer applies them while it stages x (EncEpi::a_scale)
 int enc_batchnorm(porl_enc* h, const EncBn& bn, float* x, long rows, int relu, int training, hipStream_t s,
@@ -165,10 +181,7 @@ int enc_batchnorm(porl_enc* h, const EncBn& bn, float* x, long rows, int relu, i
   }
   {
     ProfScope ps("bn_finish_kernel", s, 0.0, 0.0);
-    hipLaunchKernelGGL(bn_finish_kernel, dim3(C), dim3(64), 0, s, partial, nblocks, C, rows, h->params + bn.gamma,
-                       h->params + bn.bias, h->stats + bn.mean, h->stats + bn.var, training, (double)h->cfg.bn_eps,
-                       (double)h->cfg.bn_momentum, h->W + bn.alpha, h->W + bn.beta);
-    PORL_HIP(hipGetLastError());
+    PORL_TRY(enc_bn_finish(h, bn, partial, nblocks, rows, training, s));
   }
   if (!apply) return 0;
   const long n4 = rows * (C / 4);
@@ -200,15 +213,9 @@ int enc_pconv_mfma_launch(const float* x, const float* w, float* y, int batch, i
   a.tiles_total = batch * a.tiles_per_sample;
   // one 32-channel pass: the weight stays parked, a block walks several tiles; two passes: one tile per block
   a.tiles_per_block = CP <= 32 ? std::max(1, std::min(8, a.tiles_total / (2 * NUM_CU))) : 1;
-  const int nr_max = 128 / Ww + 4;
-  const int lds = 4 * (9 * 32 * (CP + 4) + nr_max * (Ww + 2) * (CP + 4));
-  if (lds > 150 * 1024) return -1;                              // caller falls back to the direct / patch-matrix kernels
-  static int lds_set = 0;
-  if (lds > lds_set) {
-    PORL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pconv_f32_mfma_kernel<CP>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    lds_set = lds;
-  }
+  const int lds = 4 * (pconv_mfma_pass_floats(CP) + (128 / Ww + 4) * (Ww + 2) * (CP + 4));   // weights + rows with halo
+  if (lds > ENC_LDS_LIMIT) return -1;                           // caller falls back to the direct / patch-matrix kernels
+  PORL_TRY(dyn_lds_once<&pconv_f32_mfma_kernel<CP>>(lds));
   const double rows = (double)batch * Hh * Ww;
   ProfScope ps("pconv_f32_mfma_kernel", s, 2.0 * rows * 9.0 * CP * CP, 8.0 * rows * C);
   hipLaunchKernelGGL(pconv_f32_mfma_kernel<CP>, dim3(cdiv(a.tiles_total, a.tiles_per_block)), dim3(256), lds, s, a);
@@ -240,10 +247,7 @@ int enc_pconv(porl_enc* h, const EncBlock& b, const float* x, float* y, float* c
 // one MLPBlock on x (rows, dim) in place; H x W is the position grid of its stage
 int enc_block(porl_enc* h, const EncBlock& b, float* x, long rows, int Hh, int Ww, const float* scale, int training,
               hipStream_t s) {
-  float* W = h->W;
-  float* col = W + h->ws_col;
-  float* y = W + h->ws_y;
-  float* hid = W + h->ws_h;
+  float* W = h->W; float* col = W + h->ws_col; float* y = W + h->ws_y; float* hid = W + h->ws_h;
   PORL_TRY(enc_pconv(h, b, x, y, col, rows, Hh, Ww, s));
   // W1 with the BatchNorm column statistics gathered in its epilogue; W2 adds the (DropPath-scaled) product onto
   // the shortcut in its epilogue, in place: x = x + scale * (hid W2^T)   (MLPBlock.forward, fasternet.py:186-190)
@@ -261,16 +265,10 @@ int enc_block(porl_enc* h, const EncBlock& b, float* x, long rows, int Hh, int W
   return 0;
 }
 
-
 // ---- bf16-activation mode (encoder_bf16.hpp) ---------------------------------------------------------------------------
-template <typename K>
-int enc_set_lds(K kernel, int bytes) {
-  PORL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  return 0;
-}
-
 template <int CP, int CPP, int CPN, int POS>
 int enc_pconv_bf16_launch(const __bf16* x, int ldx, const __bf16* w, __bf16* yc, int batch, int Hh, int Ww, hipStream_t s) {
+  static_assert(CPP == pconv_bf16_cpp(CP) && CPN == pconv_bf16_cpn(CP), "the kernel's padding is the packed image's");
   PconvBf16Args a{};
   a.x = x; a.yc = yc; a.w = w; a.ldx = ldx; a.Hh = Hh; a.Ww = Ww;
   a.tiles_per_sample = cdiv(Hh * Ww, POS);
@@ -278,10 +276,9 @@ int enc_pconv_bf16_launch(const __bf16* x, int ldx, const __bf16* w, __bf16* yc,
   a.tiles_total = batch * a.tiles_per_sample;
   // enough tiles per block to amortise the weight's trip into LDS (23 / 83 KB), enough blocks to fill the chip twice
   a.tiles_per_block = std::max(1, std::min(8, a.tiles_total / (2 * NUM_CU)));
-  const int lds = 2 * (9 * CPN * (CPP + 8) + a.nr_max * (Ww + 2) * (CPP + 8));
-  if (lds > 150 * 1024) PORL_FAIL(PORL_ERR_UNSUPPORTED, "partial conv tile does not fit in LDS (%d bytes)", lds);
-  static int lds_set = 0;
-  if (lds > lds_set) { PORL_TRY(enc_set_lds(&pconv_bf16_kernel<CP, CPP, CPN, POS>, lds)); lds_set = lds; }
+  const int lds = 2 * (pconv_bf16_image_elems(CP) + a.nr_max * (Ww + 2) * (CPP + 8));
+  if (lds > ENC_LDS_LIMIT) PORL_FAIL(PORL_ERR_UNSUPPORTED, "partial conv tile does not fit in LDS (%d bytes)", lds);
+  PORL_TRY((dyn_lds_once<&pconv_bf16_kernel<CP, CPP, CPN, POS>>(lds)));
   const double rows = (double)batch * Hh * Ww;
   ProfScope ps("pconv_bf16_kernel", s, 2.0 * rows * 9.0 * CP * CP, 2.0 * rows * 2.0 * CP);
   hipLaunchKernelGGL((pconv_bf16_kernel<CP, CPP, CPN, POS>), dim3(cdiv(a.tiles_total, a.tiles_per_block)), dim3(256), lds, s, a);
@@ -298,23 +295,18 @@ int enc_mlp_bf16_launch(porl_enc* h, const EncBlock& b, __bf16* x, const __bf16*
   a.w1 = reinterpret_cast<const __bf16*>(W + b.w1_bf16); a.w2 = reinterpret_cast<const __bf16*>(W + b.w2_bf16);
   a.alpha = W + b.bn.alpha; a.beta = W + b.bn.beta; a.rscale = scale; a.rs_rows = rs_rows;
   a.cstat = W + h->ws_cstat; a.out = x; a.rows = rows;
-  const long ntiles = (rows + 127) / 128;
-  const unsigned grid = (unsigned)ntiles;                          // one 128-row tile per block (see PFA in the kernel)
+  const unsigned grid = (unsigned)((rows + 127) / 128);            // one 128-row tile per block (see PFA in the kernel)
   constexpr int LDS1 = enc_mlp_lds_bytes<DIM, HID, CP>(1), LDS2 = enc_mlp_lds_bytes<DIM, HID, CP>(2);
   PORL_TRY((dyn_lds_once<&enc_mlp_bf16_kernel<DIM, HID, CP, 1>>(LDS1)));
   PORL_TRY((dyn_lds_once<&enc_mlp_bf16_kernel<DIM, HID, CP, 2>>(LDS2)));
-  if (training) {
-    {
-      ProfScope ps("enc_mlp_bf16_kernel<stats>", s, 2.0 * rows * DIM * HID, 2.0 * rows * DIM);
-      hipLaunchKernelGGL((enc_mlp_bf16_kernel<DIM, HID, CP, 1>), dim3(grid), dim3(256), LDS1, s, a);
-      PORL_HIP(hipGetLastError());
-    }
-    PORL_TRY(enc_batchnorm(h, b.bn, nullptr, rows, 1, 1, s, a.cstat, false, 128));
-  } else {
-    PORL_TRY(enc_batchnorm(h, b.bn, nullptr, rows, 1, 0, s, nullptr, false));
+  if (training) {                                                  // the statistics pass: column sums per 128 rows
+    ProfScope ps("enc_mlp_bf16_kernel<stats>", s, 2.0 * rows * DIM * HID, 2.0 * rows * DIM);
+    hipLaunchKernelGGL((enc_mlp_bf16_kernel<DIM, HID, CP, 1>), dim3(grid), dim3(256), LDS1, s, a);
+    PORL_HIP(hipGetLastError());
   }
+  PORL_TRY(enc_batchnorm(h, b.bn, nullptr, rows, 1, training, s, training ? a.cstat : nullptr, false, 128));
   ProfScope ps("enc_mlp_bf16_kernel<apply>", s, 4.0 * rows * DIM * HID, 2.0 * rows * (2.0 * DIM + CP));
-  hipLaunchKernelGGL((enc_mlp_bf16_kernel<DIM, HID, CP, 2>), dim3((unsigned)ntiles), dim3(256), LDS2, s, a);
+  hipLaunchKernelGGL((enc_mlp_bf16_kernel<DIM, HID, CP, 2>), dim3(grid), dim3(256), LDS2, s, a);
   PORL_HIP(hipGetLastError());
   return 0;
 }
@@ -322,8 +314,7 @@ int enc_mlp_bf16_launch(porl_enc* h, const EncBlock& b, __bf16* x, const __bf16*
 // one MLPBlock on bf16 x (rows, dim) in place
 int enc_block_bf16(porl_enc* h, const EncBlock& b, __bf16* x, long rows, int Hh, int Ww, const float* scale, int training,
                    hipStream_t s) {
-  float* W = h->W;
-  __bf16* yc = reinterpret_cast<__bf16*>(W + h->ws_y);
+  float* W = h->W; __bf16* yc = reinterpret_cast<__bf16*>(W + h->ws_y);
   const __bf16* wp = reinterpret_cast<const __bf16*>(W + b.wp_bf16);
   const int batch = (int)(rows / ((long)Hh * Ww));
   if (b.cp == 24) {
@@ -401,19 +392,18 @@ int porl_enc_create(const porl_enc_cfg* c, porl_enc** out) {
   h->ws_wmerge = enc_ws(h, (int64_t)E2 * E * 4);
   for (EncBlock& b : h->blocks) {
     b.wp_packed = enc_ws(h, (int64_t)b.cp * b.cp * 9); b.wp_direct = enc_ws(h, (int64_t)b.cp * b.cp * 9);
-    b.wp_mfma = enc_ws(h, (int64_t)((b.cp + 31) / 32) * 9 * 32 * (b.cp + 4));
+    b.wp_mfma = enc_ws(h, pconv_mfma_image_floats(b.cp));
   }
   // bf16-activation mode: instantiated for the reference's architecture (embed 96, mlp_ratio 2, n_div 4); other shapes
   // asked for in that mode run the bf16-OPERAND mode (fp32 tensors in memory)
   h->bf16_fused = c->bf16_operands == 2 && E == 96 && hidmax_rows1 == 192 && hid2 == 384 && E / c->n_div == 24;
   if (h->bf16_fused) {
     for (EncBlock& b : h->blocks) {
-      b.w1_bf16 = enc_ws(h, ((int64_t)b.hidden * b.dim + 1) / 2);
-      b.w2_bf16 = enc_ws(h, ((int64_t)b.hidden * b.dim + 1) / 2);
-      const int cpp = (b.cp + 15) / 16 * 16, cpn = (b.cp + 31) / 32 * 32;
-      b.wp_bf16 = enc_ws(h, (9LL * cpn * (cpp + 8) + 1) / 2);
+      b.w1_bf16 = enc_ws(h, bf16_copy_floats((int64_t)b.hidden * b.dim));
+      b.w2_bf16 = enc_ws(h, bf16_copy_floats((int64_t)b.hidden * b.dim));
+      b.wp_bf16 = enc_ws(h, bf16_copy_floats(pconv_bf16_image_elems(b.cp)));
     }
-    h->ws_wmerge_bf16 = enc_ws(h, ((int64_t)E2 * E * 4 + 1) / 2);
+    h->ws_wmerge_bf16 = enc_ws(h, bf16_copy_floats((int64_t)E2 * E * 4));
   }
   for (EncBnInfo& bi : h->bns) { bi.bn->alpha = enc_ws(h, bi.bn->C); bi.bn->beta = enc_ws(h, bi.bn->C); }
   int cmax = 0;
@@ -488,211 +478,204 @@ int porl_enc_weights_changed(porl_enc* h) {
 }  // extern "C"
 
 namespace {
+// conv weights in the k order of the patch matrices: re-made only after the weights may have changed (bind, or
+// porl_enc_weights_changed from the module's load_state_dict / .to()), not on every forward of a frozen backbone
+int enc_pack_weights(porl_enc* h, hipStream_t s) {
+  float* W = h->W; const float* P = h->params;
+  const int nm = h->E2 * h->E * 4;
+  auto pack_bf16 = [&](const float* src, int64_t dst, long n) {
+    hipLaunchKernelGGL(pack_bf16_kernel, dim3(cdiv((int)n, 256)), dim3(256), 0, s, src, reinterpret_cast<__bf16*>(W + dst), n);
+  };
+  for (const EncBlock& b : h->blocks) {
+    const dim3 grid(cdiv(b.cp * b.cp * 9, 256));
+    hipLaunchKernelGGL(permute_oihw_ohwi_kernel, grid, dim3(256), 0, s, P + b.wp, W + b.wp_packed, b.cp, b.cp, 9);
+    hipLaunchKernelGGL(pack_pconv_kernel, grid, dim3(256), 0, s, P + b.wp, W + b.wp_direct, b.cp);
+    hipLaunchKernelGGL(pack_pconv_mfma_kernel, dim3(cdiv(pconv_mfma_image_floats(b.cp), 256)), dim3(256), 0, s, P + b.wp,
+                       W + b.wp_mfma, b.cp, pconv_mfma_passes(b.cp));
+  }
+  hipLaunchKernelGGL(permute_oihw_ohwi_kernel, dim3(cdiv(nm, 256)), dim3(256), 0, s, P + h->w_merge, W + h->ws_wmerge, h->E2, h->E, 4);
+  PORL_HIP(hipGetLastError());
+  if (h->bf16_fused) {
+    for (const EncBlock& b : h->blocks) {
+      pack_bf16(P + b.w1, b.w1_bf16, (long)b.hidden * b.dim);
+      pack_bf16(P + b.w2, b.w2_bf16, (long)b.hidden * b.dim);
+      hipLaunchKernelGGL(pack_pconv_bf16_kernel, dim3(cdiv(pconv_bf16_image_elems(b.cp), 256)), dim3(256), 0, s, P + b.wp,
+                         reinterpret_cast<__bf16*>(W + b.wp_bf16), b.cp, pconv_bf16_cpn(b.cp), pconv_bf16_cpp(b.cp) + 8);
+    }
+    pack_bf16(W + h->ws_wmerge, h->ws_wmerge_bf16, nm);
+  }
+  PORL_HIP(hipGetLastError());
+  h->packed_valid = true;
+  return 0;
+}
+
+// PatchEmbed 4x4s4 + its BatchNorm -> x1 (bf16 when fused16, which implies the sparse branch); clamps a caller's own `state`
+int enc_patch_embed(porl_enc* h, const RowSrc& src, float* state, int64_t state_rs, int32_t batch, int32_t training,
+                    bool fused16, hipStream_t s) {
+  const porl_enc_cfg& c = h->cfg;
+  float* W = h->W; float* x1 = W + h->ws_x1; const float* w = h->params + h->w_patch;
+  const int E = h->E; const long rows1 = (long)batch * h->P1;
+  if (!enc_sparse_patch(h)) {
+    // rasterise (+ the in-place clamp on a caller's own tensor), then the dense 4x4 convolution; store rows go through
+    // the rasteriser alone, which only reads
+    if (state) PORL_TRY(porl_state2costmap(state, state_rs, batch, c.n_ang, c.n_dist, W + h->ws_img, s));
+    else PORL_TRY(costmap_rasterise(src, batch, c.n_ang, c.n_dist, W + h->ws_img, s));
+    {
+      ProfScope ps("patch_embed_kernel", s, 2.0 * rows1 * E * 48, 4.0 * (3.0 * batch * c.n_ang * c.n_dist + rows1 * E));
+      const size_t lds = (size_t)(12 * c.n_dist + PE_K * E) * sizeof(float);
+      hipLaunchKernelGGL(patch_embed_kernel, dim3(h->Hp, batch), dim3(256), lds, s, W + h->ws_img, w, x1, c.n_ang, c.n_dist, E);
+      PORL_HIP(hipGetLastError());
+    }
+    return enc_batchnorm(h, h->bn_patch, x1, rows1, 0, training, s);
+  }
+  // straight from the lidar state: only the ~6 % non-empty patches are convolved (statistics first, then every
+  // position is written once, already normalised); no costmap image at all
+  const CostmapGeom gm = costmap_geom(c.n_ang, c.n_dist); const int nblk = std::min(batch, 1024);
+  const EncBn& bn = h->bn_patch; double* partial = reinterpret_cast<double*>(W + h->ws_partial);
+  if (training) {
+    const size_t lds_stats = (size_t)PE_K * E * sizeof(float) + (size_t)h->P1 * (sizeof(unsigned long long) + sizeof(int));
+    ProfScope ps("patch_stats_kernel", s, 0.0, 4.0 * batch * (c.n_ang + 2));
+    PORL_TRY(dyn_lds_once<&patch_stats_kernel>((int)lds_stats));
+    hipLaunchKernelGGL(patch_stats_kernel, dim3(nblk), dim3(256), lds_stats, s, src, batch, gm, w, E, partial);
+    PORL_HIP(hipGetLastError());
+  }
+  PORL_TRY(enc_bn_finish(h, bn, partial, nblk, rows1, training, s));
+  {
+    ProfScope ps("patch_bn_kernel", s, 0.0, 4.0 * rows1 * E);
+    // patch rows per block: as many as keep >= 4 blocks per CU in the grid, at most 16 (the weight is parked once per
+    // block; measured at B = 512, bf16: 84x84 828 -> 888 updates/s, 360x256 123.1 -> 127.8, gpurun_out/r03/prow)
+    int rpb = h->tune.enc_patch_rows > 0 ? h->tune.enc_patch_rows : (int)std::max<long>(1, std::min<long>(16, (long)h->Hp * batch / (4L * NUM_CU)));
+    rpb = std::min(rpb, h->Hp);
+    const dim3 grid(cdiv(h->Hp, rpb), batch);
+    const size_t lds = (size_t)PE_K * E * sizeof(float) + (size_t)(c.n_dist / 4) * sizeof(unsigned long long);
+    if (fused16)
+      hipLaunchKernelGGL(patch_bn_kernel<true>, grid, dim3(256), lds, s, src, gm, w, E, W + bn.alpha, W + bn.beta, x1, rpb);
+    else
+      hipLaunchKernelGGL(patch_bn_kernel<false>, grid, dim3(256), lds, s, src, gm, w, E, W + bn.alpha, W + bn.beta, x1, rpb);
+    PORL_HIP(hipGetLastError());
+  }
+  return state ? clamp_state(state, state_rs, c.n_ang, batch, s) : 0;
+}
+
+// blocks [first, first + count) in place on x (rows, dim): fp32, or bf16 activations when fused16
+int enc_stage(porl_enc* h, int first, int count, float* x, long rows, int Hh, int Ww, const float* drop_scale, int32_t batch,
+              int32_t training, bool fused16, hipStream_t s) {
+  for (int i = first; i < first + count; ++i) {
+    const float* scale = drop_scale ? drop_scale + (long)i * batch : nullptr;
+    if (fused16) PORL_TRY(enc_block_bf16(h, h->blocks[i], reinterpret_cast<__bf16*>(x), rows, Hh, Ww, scale, training, s));
+    else PORL_TRY(enc_block(h, h->blocks[i], x, rows, Hh, Ww, scale, training, s));
+  }
+  return 0;
+}
+
+// PatchMerging 2x2s2, x1 -> x2, in its three forms; `cstat` (training) receives the column statistics of x2
+int enc_merge_bf16(porl_enc* h, long rows2, float* cstat, hipStream_t s) {
+  float* W = h->W; EncMergeArgs a{};
+  a.x1 = reinterpret_cast<const __bf16*>(W + h->ws_x1); a.w = reinterpret_cast<const __bf16*>(W + h->ws_wmerge_bf16);
+  a.out = reinterpret_cast<__bf16*>(W + h->ws_x2); a.cstat = cstat;
+  a.Hp = h->Hp; a.Wp = h->Wp; a.H2 = h->H2; a.W2 = h->W2; a.rows2 = rows2;
+  constexpr int MLDS = 2 * (64 * (4 * 96 + 8) + 192 * (96 + 8));
+  PORL_TRY(dyn_lds_once<&enc_merge_bf16_kernel<96>>(MLDS));
+  ProfScope ps("enc_merge_bf16_kernel", s, 2.0 * rows2 * 4.0 * h->E * h->E2, 2.0 * rows2 * (4.0 * h->E + h->E2));
+  hipLaunchKernelGGL(enc_merge_bf16_kernel<96>, dim3((unsigned)((rows2 + 63) / 64)), dim3(256), MLDS, s, a);
+  PORL_HIP(hipGetLastError());
+  return 0;
+}
+
+// the GEMM gathers each output position's patch itself — two runs of 2E contiguous floats, one image row apart —
+// through the grouped-row addressing of GemmProb (no space_to_depth copy).  Chunked per problem like enc_gemm_rows;
+// chunks start on image-row boundaries so the group arithmetic stays local.
+int enc_merge_gather(porl_enc* h, long rows2, float* cstat, hipStream_t s) {
+  const float* x1 = h->W + h->ws_x1; float* x2 = h->W + h->ws_x2;
+  const int E = h->E, E2 = h->E2, W2 = h->W2;
+  const long reach = ((1L << 31) - (1L << 22)) / (4L * 4 * E);          // rows per problem: A spans ~2x (M x 2E)
+  const long chunk = std::max<long>(W2, (reach / (32L * W2)) * (32L * W2));   // multiple of 32 rows and of W2
+  long done = 0;
+  while (done < rows2) {
+    GemmGroup g{};
+    while (done < rows2 && g.nprob < MAX_GROUP) {
+      const long m = std::min(chunk, rows2 - done);
+      // output row r (global) = (image row pair q = r / W2, ox = r % W2): its patch starts at float (r + q * W2) * 2E
+      const float* Abase = x1 + (done + (done / W2) * W2) * 2L * E;
+      GemmProb p = make_prob(GEMM_NT, Abase, 2 * E, h->W + h->ws_wmerge, 4 * E, x2 + done * E2, E2, (int)m, E2, 4 * E);
+      p.a_grp = W2; p.a_grp_jump = W2 * 2 * E; p.a_seg_tiles = 2 * E / GEMM_BK; p.a_seg_jump = h->Wp * E - 2 * E;
+      if (cstat) p.cstat = cstat + (done / 32) * 2 * E2;
+      g.p[g.nprob++] = p;
+      done += m;
+    }
+    g.single_buffer = (h->tune.enc_gemm_sb & 2) ? 1 : 0;
+    PORL_TRY(launch_group(g, (h->tune.enc_gemm_sb & 2) ? TILE_64x64 : TILE_128x64, h->tune, s));
+  }
+  return 0;
+}
+
+int enc_merge_s2d(porl_enc* h, long rows1, long rows2, const EncEpi& em, hipStream_t s) {
+  float* W = h->W; const int E = h->E, E2 = h->E2;
+  {
+    ProfScope ps("space_to_depth_kernel", s, 0.0, 8.0 * rows1 * E);
+    hipLaunchKernelGGL(space_to_depth_kernel, dim3(sweep_blocks(rows2 * 4 * (E / 4))), dim3(256), 0, s, W + h->ws_x1,
+                       W + h->ws_col, rows2, h->Hp, h->Wp, E);
+    PORL_HIP(hipGetLastError());
+  }
+  return enc_gemm_rows(h, s, W + h->ws_col, 4 * E, rows2, W + h->ws_wmerge, E2, 4 * E, W + h->ws_x2, E2, nullptr, ACT_NONE, em);
+}
+
+// the merge and its BatchNorm (no ReLU), applied to x2 in place
+int enc_merge(porl_enc* h, long rows1, long rows2, int32_t training, bool fused16, hipStream_t s) {
+  float* W = h->W; const int E = h->E, E2 = h->E2;
+  EncEpi em; em.bf16 = h->cfg.bf16_operands != 0;
+  if (training) em.cstat = W + h->ws_cstat;
+  if (fused16) PORL_TRY(enc_merge_bf16(h, rows2, em.cstat, s));
+  else if ((2 * E) % GEMM_BK == 0 && !h->tune.enc_s2d && h->Hp % 2 == 0 && h->Wp % 2 == 0 && !em.bf16)
+    PORL_TRY(enc_merge_gather(h, rows2, em.cstat, s));
+  else PORL_TRY(enc_merge_s2d(h, rows1, rows2, em, s));
+  PORL_TRY(enc_batchnorm(h, h->bn_merge, W + h->ws_x2, rows2, 0, training, s, em.cstat, !fused16));
+  if (!fused16) return 0;
+  const long n8 = rows2 * (E2 / 8);
+  ProfScope ps("bn_apply_bf16_kernel", s, 0.0, 4.0 * rows2 * E2);
+  hipLaunchKernelGGL(bn_apply_bf16_kernel, dim3(sweep_blocks(n8)), dim3(256), 0, s, reinterpret_cast<__bf16*>(W + h->ws_x2), n8,
+                     E2 / 8, W + h->bn_merge.alpha, W + h->bn_merge.beta);
+  PORL_HIP(hipGetLastError());
+  return 0;
+}
+
+// global average pool of x2 -> the pooled vector (fp32 in both modes)
+int enc_pool(porl_enc* h, int32_t batch, bool fused16, hipStream_t s) {
+  float* x2 = h->W + h->ws_x2; float* pool = h->W + h->ws_pool;
+  const long rows2 = (long)batch * h->P2;
+  ProfScope ps(fused16 ? "gap_bf16_kernel" : "gap_kernel", s, 0.0, (fused16 ? 2.0 : 4.0) * rows2 * h->E2);
+  if (fused16)
+    hipLaunchKernelGGL(gap_bf16_kernel, dim3(batch), dim3(256), 0, s, reinterpret_cast<const __bf16*>(x2), pool, h->P2, h->E2);
+  else
+    hipLaunchKernelGGL(gap_kernel, dim3(cdiv(h->E2, 64), batch), dim3(256), 0, s, x2, pool, h->P2, h->E2);
+  PORL_HIP(hipGetLastError());
+  return 0;
+}
+
+// 1x1 (2E -> feature_dim) + ReLU, then the Linear head into the caller's `features`
+int enc_head(porl_enc* h, int32_t batch, float* features, int64_t feat_rs, hipStream_t s) {
+  const porl_enc_cfg& c = h->cfg; float* W = h->W;
+  PORL_TRY(enc_gemm_rows(h, s, W + h->ws_pool, h->E2, batch, h->params + h->w_pre, c.feature_dim, h->E2, W + h->ws_feat,
+                         c.feature_dim, nullptr, ACT_RELU));
+  return enc_gemm_rows(h, s, W + h->ws_feat, c.feature_dim, batch, h->params + h->w_head, c.num_classes, c.feature_dim,
+                       features, (int)feat_rs, h->params + h->b_head, ACT_NONE);
+}
+
 // The forward on a row source.  `state` is the caller's own dense tensor (porl_enc_forward: entries > 8 are zeroed in it
 // afterwards, the reference's side effect) or null (porl_enc_forward_rows: the source is only read).
 int enc_forward_src(porl_enc* h, const RowSrc& src, float* state, int64_t state_rs, int32_t batch, int32_t training,
                     const float* drop_scale, float* features, int64_t feat_rs, void* stream) {
   DevGuard _dg(h->device);
-  hipStream_t s = (hipStream_t)stream;
-  const porl_enc_cfg& c = h->cfg;
-  float* W = h->W;
-  const int E = h->E, E2 = h->E2;
+  hipStream_t s = (hipStream_t)stream; const porl_enc_cfg& c = h->cfg;
   const long rows1 = (long)batch * h->P1, rows2 = (long)batch * h->P2;
-
-  // conv weights in the k order of the patch matrices: re-made only after the weights may have changed (bind, or
-  // porl_enc_weights_changed from the module's load_state_dict / .to()), not on every forward of a frozen backbone
-  if (!h->packed_valid) {
-  for (const EncBlock& b : h->blocks) {
-    hipLaunchKernelGGL(permute_oihw_ohwi_kernel, dim3(cdiv(b.cp * b.cp * 9, 256)), dim3(256), 0, s, h->params + b.wp,
-                       W + b.wp_packed, b.cp, b.cp, 9);
-    hipLaunchKernelGGL(pack_pconv_kernel, dim3(cdiv(b.cp * b.cp * 9, 256)), dim3(256), 0, s, h->params + b.wp,
-                       W + b.wp_direct, b.cp);
-    hipLaunchKernelGGL(pack_pconv_mfma_kernel, dim3(cdiv(((b.cp + 31) / 32) * 9 * 32 * (b.cp + 4), 256)), dim3(256), 0, s,
-                       h->params + b.wp, W + b.wp_mfma, b.cp, (b.cp + 31) / 32);
-  }
-  hipLaunchKernelGGL(permute_oihw_ohwi_kernel, dim3(cdiv(E2 * E * 4, 256)), dim3(256), 0, s, h->params + h->w_merge,
-                     W + h->ws_wmerge, E2, E, 4);
-  PORL_HIP(hipGetLastError());
-  if (h->bf16_fused) {
-    for (const EncBlock& b : h->blocks) {
-      const long n = (long)b.hidden * b.dim;
-      hipLaunchKernelGGL(pack_bf16_kernel, dim3(cdiv((int)n, 256)), dim3(256), 0, s, h->params + b.w1, reinterpret_cast<__bf16*>(W + b.w1_bf16), n);
-      hipLaunchKernelGGL(pack_bf16_kernel, dim3(cdiv((int)n, 256)), dim3(256), 0, s, h->params + b.w2, reinterpret_cast<__bf16*>(W + b.w2_bf16), n);
-      const int cpp = (b.cp + 15) / 16 * 16, cpn = (b.cp + 31) / 32 * 32;
-      hipLaunchKernelGGL(pack_pconv_bf16_kernel, dim3(cdiv(9 * cpn * (cpp + 8), 256)), dim3(256), 0, s, h->params + b.wp,
-                         reinterpret_cast<__bf16*>(W + b.wp_bf16), b.cp, cpn, cpp + 8);
-    }
-    const long nm = (long)E2 * E * 4;
-    hipLaunchKernelGGL(pack_bf16_kernel, dim3(cdiv((int)nm, 256)), dim3(256), 0, s, W + h->ws_wmerge,
-                       reinterpret_cast<__bf16*>(W + h->ws_wmerge_bf16), nm);
-    PORL_HIP(hipGetLastError());
-  }
-  h->packed_valid = true;
-  }
-
-  float* x1 = W + h->ws_x1;
-  float* x2 = W + h->ws_x2;
-  const bool sparse_patch = enc_sparse_patch(h);
   const bool fused16 = enc_fused16(h);
-  if (sparse_patch) {
-    // PatchEmbed + its BatchNorm straight from the lidar state: only the ~6 % non-empty patches are convolved
-    // (statistics first, then every position is written once, already normalised); no costmap image at all
-    const double pi = 3.14159265358979323846;
-    CostmapGeom gm{};
-    gm.n_ang = c.n_ang; gm.n_dist = c.n_dist;
-    gm.dist_inc = (float)((4.0 + 1e-4) / c.n_dist);                     // the constants of porl_state2costmap
-    gm.ang_inc = (float)((2.0 * pi + 1e-4) / c.n_ang);
-    gm.deg_min = (float)(-pi + (2.0 * pi + 2e-4) / c.n_ang); gm.deg_max = (float)(pi - (2.0 * pi + 2e-4) / c.n_ang);
-    gm.dist_max = (float)(4.0 - 4.0 / c.n_dist);
-    const size_t lds = (size_t)PE_K * E * sizeof(float) + (size_t)(c.n_dist / 4) * sizeof(unsigned long long);
-    double* partial = reinterpret_cast<double*>(W + h->ws_partial);
-    const int nblk = std::min(batch, 1024);
-    if (training) {
-      ProfScope ps("patch_stats_kernel", s, 0.0, 4.0 * batch * (c.n_ang + 2));
-      const size_t lds_stats = (size_t)PE_K * E * sizeof(float) + (size_t)h->P1 * (sizeof(unsigned long long) + sizeof(int));
-      static size_t lds_attr = 0;
-      if (lds_stats > lds_attr) {
-        PORL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_stats_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_stats));
-        lds_attr = lds_stats;
-      }
-      hipLaunchKernelGGL(patch_stats_kernel, dim3(nblk), dim3(256), lds_stats, s, src, batch, gm,
-                         h->params + h->w_patch, E, partial);
-      PORL_HIP(hipGetLastError());
-    }
-    const EncBn& bn = h->bn_patch;
-    hipLaunchKernelGGL(bn_finish_kernel, dim3(E), dim3(64), 0, s, partial, nblk, E, rows1, h->params + bn.gamma,
-                       h->params + bn.bias, h->stats + bn.mean, h->stats + bn.var, training, (double)c.bn_eps,
-                       (double)c.bn_momentum, W + bn.alpha, W + bn.beta);
-    PORL_HIP(hipGetLastError());
-    {
-      ProfScope ps("patch_bn_kernel", s, 0.0, 4.0 * rows1 * E);
-      // patch rows per block: as many as keep >= 4 blocks per CU in the grid, at most 16 (the weight is parked once per
-      // block; measured at B = 512, bf16: 84x84 828 -> 888 updates/s, 360x256 123.1 -> 127.8, gpurun_out/r03/prow)
-      int rpb = h->tune.enc_patch_rows > 0 ? h->tune.enc_patch_rows : (int)std::max<long>(1, std::min<long>(16, (long)h->Hp * batch / (4L * NUM_CU)));
-      rpb = std::min(rpb, h->Hp);
-      const dim3 grid(cdiv(h->Hp, rpb), batch);
-      if (fused16)
-        hipLaunchKernelGGL(patch_bn_kernel<true>, grid, dim3(256), lds, s, src, gm,
-                           h->params + h->w_patch, E, W + bn.alpha, W + bn.beta, x1, rpb);
-      else
-        hipLaunchKernelGGL(patch_bn_kernel<false>, grid, dim3(256), lds, s, src, gm,
-                           h->params + h->w_patch, E, W + bn.alpha, W + bn.beta, x1, rpb);
-      PORL_HIP(hipGetLastError());
-    }
-    if (state) {                                        // the reference's in-place side effect (util/costmap.py:17)
-      const long n = (long)batch * (c.n_ang + 2);
-      hipLaunchKernelGGL(clamp_gt8_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 1024)), dim3(256), 0, s, state,
-                         (long)state_rs, c.n_ang + 2, batch);
-      PORL_HIP(hipGetLastError());
-    }
-  } else {
-    // rasterise (+ the in-place clamp on a caller's own tensor), then the dense 4x4 convolution; store rows go through
-    // the rasteriser alone, which only reads
-    if (state) PORL_TRY(porl_state2costmap(state, state_rs, batch, c.n_ang, c.n_dist, W + h->ws_img, stream));
-    else PORL_TRY(costmap_rasterise(src, batch, c.n_ang, c.n_dist, W + h->ws_img, s));
-    {
-      ProfScope ps("patch_embed_kernel", s, 2.0 * rows1 * E * 48, 4.0 * (3.0 * batch * c.n_ang * c.n_dist + rows1 * E));
-      const size_t lds = (size_t)(12 * c.n_dist + PE_K * E) * sizeof(float);
-      hipLaunchKernelGGL(patch_embed_kernel, dim3(h->Hp, batch), dim3(256), lds, s, W + h->ws_img, h->params + h->w_patch,
-                         x1, c.n_ang, c.n_dist, E);
-      PORL_HIP(hipGetLastError());
-    }
-    PORL_TRY(enc_batchnorm(h, h->bn_patch, x1, rows1, 0, training, s));
-  }
-  if (fused16) {
-    // ---- the rest of the backbone on bf16 activations (encoder_bf16.hpp) ------------------------------------------------
-    __bf16* x1b = reinterpret_cast<__bf16*>(x1);
-    __bf16* x2b = reinterpret_cast<__bf16*>(x2);
-    for (int i = 0; i < c.depth0; ++i)
-      PORL_TRY(enc_block_bf16(h, h->blocks[i], x1b, rows1, h->Hp, h->Wp, drop_scale ? drop_scale + (long)i * batch : nullptr,
-                              training, s));
-    {
-      EncMergeArgs a{};
-      a.x1 = x1b; a.w = reinterpret_cast<const __bf16*>(W + h->ws_wmerge_bf16); a.out = x2b;
-      a.cstat = training ? W + h->ws_cstat : nullptr;
-      a.Hp = h->Hp; a.Wp = h->Wp; a.H2 = h->H2; a.W2 = h->W2; a.rows2 = rows2;
-      constexpr int MLDS = 2 * (64 * (4 * 96 + 8) + 192 * (96 + 8));
-      PORL_TRY(dyn_lds_once<&enc_merge_bf16_kernel<96>>(MLDS));
-      ProfScope ps("enc_merge_bf16_kernel", s, 2.0 * rows2 * 4.0 * E * E2, 2.0 * rows2 * (4.0 * E + E2));
-      hipLaunchKernelGGL(enc_merge_bf16_kernel<96>, dim3((unsigned)((rows2 + 63) / 64)), dim3(256), MLDS, s, a);
-      PORL_HIP(hipGetLastError());
-    }
-    PORL_TRY(enc_batchnorm(h, h->bn_merge, nullptr, rows2, 0, training, s, training ? W + h->ws_cstat : nullptr, false));
-    {
-      const long n8 = rows2 * (E2 / 8);
-      ProfScope ps("bn_apply_bf16_kernel", s, 0.0, 4.0 * rows2 * E2);
-      hipLaunchKernelGGL(bn_apply_bf16_kernel, dim3(sweep_blocks(n8)), dim3(256), 0, s, x2b, n8, E2 / 8, W + h->bn_merge.alpha,
-                         W + h->bn_merge.beta);
-      PORL_HIP(hipGetLastError());
-    }
-    for (int i = c.depth0; i < c.depth0 + c.depth1; ++i)
-      PORL_TRY(enc_block_bf16(h, h->blocks[i], x2b, rows2, h->H2, h->W2, drop_scale ? drop_scale + (long)i * batch : nullptr,
-                              training, s));
-    {
-      ProfScope ps("gap_bf16_kernel", s, 0.0, 2.0 * rows2 * E2);
-      hipLaunchKernelGGL(gap_bf16_kernel, dim3(batch), dim3(256), 0, s, x2b, W + h->ws_pool, h->P2, E2);
-      PORL_HIP(hipGetLastError());
-    }
-    PORL_TRY(enc_gemm_rows(h, s, W + h->ws_pool, E2, batch, h->params + h->w_pre, c.feature_dim, E2, W + h->ws_feat,
-                           c.feature_dim, nullptr, ACT_RELU));
-    PORL_TRY(enc_gemm_rows(h, s, W + h->ws_feat, c.feature_dim, batch, h->params + h->w_head, c.num_classes, c.feature_dim,
-                           features, (int)feat_rs, h->params + h->b_head, ACT_NONE));
-    return PORL_OK;
-  }
-  for (int i = 0; i < c.depth0; ++i)
-    PORL_TRY(enc_block(h, h->blocks[i], x1, rows1, h->Hp, h->Wp, drop_scale ? drop_scale + (long)i * batch : nullptr,
-                       training, s));
-  // PatchMerging 2x2s2: the GEMM gathers each output position's patch itself — two runs of 2E contiguous floats, one
-  // image row apart — through the grouped-row addressing of GemmProb (no space_to_depth copy).  Chunked per problem
-  // like enc_gemm_rows; chunks start on image-row boundaries so the group arithmetic stays local.
-  EncEpi em;
-  em.bf16 = c.bf16_operands != 0;
-  if (training) em.cstat = W + h->ws_cstat;
-  if ((2 * E) % GEMM_BK == 0 && !h->tune.enc_s2d && h->Hp % 2 == 0 && h->Wp % 2 == 0 && !em.bf16) {
-    const int W2 = h->W2;
-    const long reach = ((1L << 31) - (1L << 22)) / (4L * 4 * E);          // rows per problem: A spans ~2x (M x 2E)
-    const long chunk = std::max<long>(W2, (reach / (32L * W2)) * (32L * W2));   // multiple of 32 rows and of W2
-    long done = 0;
-    while (done < rows2) {
-      GemmGroup g{};
-      while (done < rows2 && g.nprob < MAX_GROUP) {
-        const long m = std::min(chunk, rows2 - done);
-        // output row r (global) = (image row pair q = r / W2, ox = r % W2): its patch starts at float (r + q * W2) * 2E
-        const float* Abase = x1 + (done + (done / W2) * W2) * 2L * E;
-        GemmProb p = make_prob(GEMM_NT, Abase, 2 * E, W + h->ws_wmerge, 4 * E, x2 + done * E2, E2, (int)m, E2, 4 * E);
-        p.a_grp = W2; p.a_grp_jump = W2 * 2 * E; p.a_seg_tiles = 2 * E / GEMM_BK; p.a_seg_jump = h->Wp * E - 2 * E;
-        if (em.cstat) p.cstat = em.cstat + (done / 32) * 2 * E2;
-        g.p[g.nprob++] = p;
-        done += m;
-      }
-      g.single_buffer = (h->tune.enc_gemm_sb & 2) ? 1 : 0;
-      PORL_TRY(launch_group(g, (h->tune.enc_gemm_sb & 2) ? TILE_64x64 : TILE_128x64, h->tune, s));
-    }
-  } else {
-    {
-      const long items = rows2 * 4 * (E / 4);
-      ProfScope ps("space_to_depth_kernel", s, 0.0, 8.0 * rows1 * E);
-      hipLaunchKernelGGL(space_to_depth_kernel, dim3(sweep_blocks(items)), dim3(256), 0, s, x1, W + h->ws_col, rows2, h->Hp,
-                         h->Wp, E);
-      PORL_HIP(hipGetLastError());
-    }
-    PORL_TRY(enc_gemm_rows(h, s, W + h->ws_col, 4 * E, rows2, W + h->ws_wmerge, E2, 4 * E, x2, E2, nullptr, ACT_NONE, em));
-  }
-  PORL_TRY(enc_batchnorm(h, h->bn_merge, x2, rows2, 0, training, s, em.cstat));
-  for (int i = c.depth0; i < c.depth0 + c.depth1; ++i)
-    PORL_TRY(enc_block(h, h->blocks[i], x2, rows2, h->H2, h->W2, drop_scale ? drop_scale + (long)i * batch : nullptr,
-                       training, s));
-  {
-    ProfScope ps("gap_kernel", s, 0.0, 4.0 * rows2 * E2);
-    hipLaunchKernelGGL(gap_kernel, dim3(cdiv(E2, 64), batch), dim3(256), 0, s, x2, W + h->ws_pool, h->P2, E2);
-    PORL_HIP(hipGetLastError());
-  }
-  PORL_TRY(enc_gemm_rows(h, s, W + h->ws_pool, E2, batch, h->params + h->w_pre, c.feature_dim, E2, W + h->ws_feat,
-                         c.feature_dim, nullptr, ACT_RELU));
-  PORL_TRY(enc_gemm_rows(h, s, W + h->ws_feat, c.feature_dim, batch, h->params + h->w_head, c.num_classes, c.feature_dim,
-                         features, (int)feat_rs, h->params + h->b_head, ACT_NONE));
-  return PORL_OK;
+  if (!h->packed_valid) PORL_TRY(enc_pack_weights(h, s));
+  PORL_TRY(enc_patch_embed(h, src, state, state_rs, batch, training, fused16, s));
+  PORL_TRY(enc_stage(h, 0, c.depth0, h->W + h->ws_x1, rows1, h->Hp, h->Wp, drop_scale, batch, training, fused16, s));
+  PORL_TRY(enc_merge(h, rows1, rows2, training, fused16, s));
+  PORL_TRY(enc_stage(h, c.depth0, c.depth1, h->W + h->ws_x2, rows2, h->H2, h->W2, drop_scale, batch, training, fused16, s));
+  PORL_TRY(enc_pool(h, batch, fused16, s));
+  return enc_head(h, batch, features, feat_rs, s);
 }
 }  // namespace
 

@@ -33,6 +33,12 @@ __device__ __forceinline__ u32x4 ld16_or_zero(const __bf16* base, long off, bool
   return ok ? v : u32x4{0u, 0u, 0u, 0u};
 }
 
+// workspace floats holding n bf16 values; the partial-conv image below pads ci to CPP (+ 8: the LDS pixel stride), oc to CPN
+constexpr int64_t bf16_copy_floats(int64_t n) { return (n + 1) / 2; }
+constexpr int pconv_bf16_cpp(int cp) { return (cp + 15) / 16 * 16; }
+constexpr int pconv_bf16_cpn(int cp) { return (cp + 31) / 32 * 32; }
+constexpr int pconv_bf16_image_elems(int cp) { return 9 * pconv_bf16_cpn(cp) * (pconv_bf16_cpp(cp) + 8); }
+
 // fp32 -> bf16 (round to nearest even), linear
 __global__ void pack_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) dst[i] = (__bf16)src[i];

@@ -1232,6 +1232,15 @@ __global__ __launch_bounds__(256) void cql_penalty_kernel(const float* __restric
 //     exactly as the reference's advanced indexing does (dist bin 0 lights bin n_dist-1)
 // Ranges that would index past n_dist-1 make the reference raise; here they are dropped.
 // ---------------------------------------------------------------------------------------------------
+struct CostmapGeom { int n_ang, n_dist; float dist_inc, ang_inc, deg_min, deg_max, dist_max; };
+
+// constants exactly as util/costmap.py:19-20,34,45 forms them (python doubles rounded to fp32 at the tensor op)
+inline CostmapGeom costmap_geom(int n_ang, int n_dist) {
+  const double pi = 3.14159265358979323846;
+  return {n_ang, n_dist, (float)((4.0 + 1e-4) / n_dist), (float)((2.0 * pi + 1e-4) / n_ang),
+          (float)(-pi + (2.0 * pi + 2e-4) / n_ang), (float)(pi - (2.0 * pi + 2e-4) / n_ang), (float)(4.0 - 4.0 / n_dist)};
+}
+
 __global__ void costmap_kernel(const RowSrc state, int n_ang, int n_dist,
                                float dist_inc, float ang_inc, float deg_min, float deg_max, float dist_max,
                                float* __restrict__ out) {

@@ -83,14 +83,15 @@ int device_of(const void* p) {
   return a.type == hipMemoryTypeDevice ? a.device : -1;
 }
 
-// Raises Kernel's dynamic-LDS limit above the 64 KiB default, once per process: on the first call, and again only if
-// that call failed.  One flag per kernel, so a launch site that needs several raised lists them one after another.
+// Raises Kernel's dynamic-LDS limit above the 64 KiB default whenever `bytes` exceeds what this process has already set
+// for it: with a constant size once, on the first call (again only if that failed); with a shape's size whenever it grows.
+// One record per kernel, so a launch site that needs several raised lists them one after another.
 template <auto Kernel>
 int dyn_lds_once(int bytes) {
-  static bool done = false;
-  if (!done) {
+  static int set = 0;
+  if (bytes > set) {
     PORL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    done = true;
+    set = bytes;
   }
   return 0;
 }
@@ -753,14 +754,17 @@ int porl_tune_set_ptr(const char* key, void* ptr) {
 // the rasteriser alone on any row source (reads only): porl_state2costmap, and the encoder's dense patch path on rows of a
 // replay store (encoder_api.inc)
 static int costmap_rasterise(const RowSrc& src, int32_t batch, int32_t n_ang, int32_t n_dist, float* out, hipStream_t s) {
-  // constants exactly as util/costmap.py:19-20,34,45 forms them (python doubles rounded to fp32 at the tensor op)
-  const double pi = 3.14159265358979323846;
-  const float dist_inc = (float)((4.0 + 1e-4) / n_dist);
-  const float ang_inc = (float)((2.0 * pi + 1e-4) / n_ang);
-  const float deg_min = (float)(-pi + (2.0 * pi + 2e-4) / n_ang), deg_max = (float)(pi - (2.0 * pi + 2e-4) / n_ang);
-  const float dist_max = (float)(4.0 - 4.0 / n_dist);
-  hipLaunchKernelGGL(costmap_kernel, dim3(n_ang, batch), dim3(std::min(256, n_dist)), 0, s, src, n_ang, n_dist, dist_inc,
-                     ang_inc, deg_min, deg_max, dist_max, out);
+  const CostmapGeom g = costmap_geom(n_ang, n_dist);
+  hipLaunchKernelGGL(costmap_kernel, dim3(n_ang, batch), dim3(std::min(256, n_dist)), 0, s, src, n_ang, n_dist, g.dist_inc,
+                     g.ang_inc, g.deg_min, g.deg_max, g.dist_max, out);
+  PORL_HIP(hipGetLastError());
+  return PORL_OK;
+}
+// the reference's in-place side effect (util/costmap.py:17) on a caller's own (batch, n_ang + 2) tensor
+static int clamp_state(float* state, int64_t state_rs, int32_t n_ang, int32_t batch, hipStream_t s) {
+  const long n = (long)batch * (n_ang + 2);
+  hipLaunchKernelGGL(clamp_gt8_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 1024)), dim3(256), 0, s, state,
+                     (long)state_rs, n_ang + 2, batch);
   PORL_HIP(hipGetLastError());
   return PORL_OK;
 }
@@ -772,11 +776,7 @@ int porl_state2costmap(float* state, int64_t state_rs, int32_t batch, int32_t n_
   DevGuard _dg(device_of(out));
   hipStream_t s = (hipStream_t)stream;
   PORL_TRY(costmap_rasterise(RowSrc{state, (long)state_rs, nullptr, 0}, batch, n_ang, n_dist, out, s));
-  const long n = (long)batch * (n_ang + 2);
-  hipLaunchKernelGGL(clamp_gt8_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 1024)), dim3(256), 0, s, state,
-                     (long)state_rs, n_ang + 2, batch);
-  PORL_HIP(hipGetLastError());
-  return PORL_OK;
+  return clamp_state(state, state_rs, n_ang, batch, s);
 }
 
 // ---- dataset labelling (astar.hpp) ---------------------------------------------------------------------------------
